@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: audio samples/s of WaveGlow-256ch forward + NLL backward on 16 000-sample segments.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--no-cpu] [--no-inverse] [--spawn]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--no-cpu] [--no-inverse] [--spawn] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -202,7 +202,8 @@ def cpu_baseline():
     oracle/torch_cpu.py -- the path's algorithm restated on the library the reference itself runs on (ATen's CPU convolutions, a local
     autograd graph per WN, activations rebuilt flow by flow), pinned to the reference's golden vectors by tests/test_oracle_golden.py --
     `value` = the C2 network on ALL cores the host grants (min(physical cores, cgroup CPU quota)): worker processes x threads in the split a
-    short C1 probe finds fastest, one 16000-sample segment per process (batch items are independent units), 1 warm-up + 3 timed steps.  Next to it one process alone (`single_process`, C2 B=1,
+    short C1 probe finds fastest (at most oracle/torch_cpu.MAX_WORKERS = 5 processes, so the figure is capped where more processes x fewer
+    threads would be faster), one 16000-sample segment per process (batch items are independent units), 1 warm-up + 3 timed steps.  Next to it one process alone (`single_process`, C2 B=1,
     its fastest thread count) and C1 (64ch, 6 flows, B=2, seg 4000).  The plain-C oracle (oracle/wg_oracle.c, OpenMP), which the parity tests use as their
     checker, is timed next to it on C2 B=1 as `c_port`."""
     sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
@@ -250,6 +251,9 @@ def cpu_baseline():
     logical, quota, _ = torch_cpu.host_cpu_budget()
     budget = max(1, min(phys, int(quota + 0.5)) if quota else phys)
     cands = sorted({(max(1, budget // t), t) for t in (8, 4, 2, 1) if budget // t >= 1} | {(min(2 * budget, phys), 1)})
+    # (at most torch_cpu.MAX_WORKERS worker processes: a split with more keeps its thread total over the capped process count)
+    cap = torch_cpu.MAX_WORKERS
+    cands = sorted({(w_, t_) if w_ <= cap else (cap, -(-w_ * t_ // cap)) for w_, t_ in cands})
     split_probe = {}
     c1_tab = fill.table(fill.model_param_specs(c1), fill.fill_params(fill.model_param_specs(c1), "c1/"))
     c1_audio, c1_h = fill.inputs("c1/cpu2", 2, 4000, 16, c1["n_mels"])
@@ -258,7 +262,8 @@ def cpu_baseline():
     best = max(split_probe, key=split_probe.get)
     workers, wthreads = (int(v) for v in best.split("x"))
     allcore = torch_cpu.time_parallel(C2, tab, audio, h, SIGMA, workers=workers, threads=wthreads, runs=3)
-    allcore.update({"cgroup_quota_cpus": quota, "logical_cpus": logical, "core_budget": budget, "split_probe_c1_samples_per_s": split_probe})
+    allcore.update({"cgroup_quota_cpus": quota, "logical_cpus": logical, "core_budget": budget, "split_probe_c1_samples_per_s": split_probe,
+                    "max_worker_processes": cap})
     total = sum(r["median_s"] * (r["runs"] + 1) for r in res.values()) + allcore["wall_s"] * 4.0 / 3.0
     # the C port: capped at 64 OpenMP threads (its loops expose 64-128 independent row blocks; more threads measured slower)
     oc = orc.make_config(**C2)
@@ -270,10 +275,11 @@ def cpu_baseline():
             "implementation": "torch-cpu: oracle/torch_cpu.py, the step restated on ATen's CPU kernels (F.conv1d / MKLDNN), "
                               "constant-memory backward with a local autograd graph per WN; torch %s" % torch.__version__,
             "cpu_model": _cpu_model(),
-            "sample": "WaveGlow-256ch 12 flows fwd+NLL+bwd, one 16000-sample segment per worker process: %d processes x %d threads, 1 warm-up + 3 "
-                      "timed steps each, released together; value = processes x 3 x 16000 / (last end - first start).  Beside it: one "
-                      "process alone (`single_process`), C1 (64ch, 6 flows, B=2, seg 4000) and the plain-C oracle; about %.0f s of CPU work in all"
-                      % (allcore["workers"], allcore["threads_per_worker"], total + cport["median_s"] * 3),
+            "sample": "WaveGlow-256ch 12 flows fwd+NLL+bwd, one 16000-sample segment per worker process: %d processes x %d threads (at most %d "
+                      "worker processes), 1 warm-up + 3 timed steps each, released together; value = processes x 3 x 16000 / (last end - first "
+                      "start).  Beside it: one process alone (`single_process`), C1 (64ch, 6 flows, B=2, seg 4000) and the plain-C oracle; about "
+                      "%.0f s of CPU work in all" % (allcore["workers"], allcore["threads_per_worker"], cap, total + cport["median_s"] * 3),
+            "max_worker_processes": cap,
             "all_core": allcore, "single_process": single, "configs": res, "c_port": cport,
             "thread_probe_c1_s": {str(k): v for k, v in probe.items()}, "physical_cores": phys,
             "build_container_reference": {
@@ -519,10 +525,18 @@ def make_workload(name, dev, batch, rank):
       waveflow  configs/waveflow_LJ_speech.json   batch 12 x 16000, sigma 0.7   autograd (_WaveFlowFn) + ONE 24 MB gradient collective
       wsrglow   configs/wsrglow_vctk_2x.json      batch 12 x 8192,  sigma 1.0   FlowTrainer (+ the embedding-table bucket)
     step() = forward + NLL + backward to every parameter gradient (+ the mean all-reduce when the process group has > 1 rank or the
-    collectives are forced); weights re-packed every step, inputs resident in HBM."""
+    collectives are forced); weights re-packed every step, inputs resident in HBM.  last["out"] = (loss, z, logdet) of the latest step
+    (detached), for --dump-outputs; the gradients stay in p.grad."""
     import constant_memory_waveglow_amd as cm
     from constant_memory_waveglow_amd.parallel import FlowTrainer, GradSync
     g = torch.Generator(device=dev).manual_seed(1234 + rank)
+    last = {}
+
+    def trainer_step(trainer, x, h):
+        loss, z, logdet = trainer.step(x, h)
+        last["out"] = (loss.detach(), z.detach(), logdet.detach())
+        return loss
+
     if name == "waveglow":
         B = batch or 24
         model = build_model(dev)
@@ -530,8 +544,8 @@ def make_workload(name, dev, batch, rank):
         x = torch.rand(B, SEG, device=dev, generator=g) * 2 - 1          # as tests/test_fwd_bwd.py:28 upstream
         h = torch.randn(B, C2["n_mels"], FRAMES, device=dev, generator=g)
         kcat = C2["radix"] * C2["residual_channels"] + C2["n_mels"]
-        return dict(model=model, trainer=trainer, sync=trainer.sync, batch=B, segment=SEG, x=x, h=h, generator=g,
-                    step=lambda: trainer.step(x, h)[0], metric="audio samples/sec (fwd+bwd) WaveGlow-256ch seg=16000",
+        return dict(model=model, trainer=trainer, sync=trainer.sync, batch=B, segment=SEG, x=x, h=h, generator=g, last=last,
+                    step=lambda: trainer_step(trainer, x, h), metric="audio samples/sec (fwd+bwd) WaveGlow-256ch seg=16000",
                     workload="WaveGlow 256ch, 12 flows, seg=16000, batch=%d per GPU (waveglow_LJ_speech.json), forward + NLL + "
                              "constant-memory backward" % B,
                     step_flop_per_sample=STEP_FLOP_PER_SAMPLE, gate_launches_per_step=2 * C2["flows"] * C2["depth"],
@@ -552,8 +566,8 @@ def make_workload(name, dev, batch, rank):
         # per time step of 16 samples and flow: 8 layers x 2 x (3 x 256 + 3659) x 512 (conv + conditioning) + W_o + start / end
         kcat = 3 * 256 + 3659
         fwd = (8 * (2 * kcat * 512 + 2 * 256 * 512) - 2 * 256 * 256 + 2 * 256 * 16) * 12 / 16.0
-        return dict(model=model, trainer=trainer, sync=trainer.sync, batch=B, segment=seg, x=x, h=c, generator=g,
-                    step=lambda: trainer.step(x, c.clone())[0], metric="audio samples/sec (fwd+bwd) WSRGlow 2x seg=8192",
+        return dict(model=model, trainer=trainer, sync=trainer.sync, batch=B, segment=seg, x=x, h=c, generator=g, last=last,
+                    step=lambda: trainer_step(trainer, x, c.clone()), metric="audio samples/sec (fwd+bwd) WSRGlow 2x seg=8192",
                     workload="WSRGlow 2x (wsrglow_vctk_2x.json: 12 flows, n_group 16, 3659 conditioning channels, 229.7 M parameters), "
                              "seg=8192, batch=%d per GPU, conditioning front-end + forward + NLL + constant-memory backward" % B,
                     step_flop_per_sample=3.0 * fwd, gate_launches_per_step=2 * 12 * 8,
@@ -581,16 +595,51 @@ def make_workload(name, dev, batch, rank):
         loss = crit(z, ld)
         loss.backward()
         sync.all_reduce_params(params)
+        last["out"] = (loss.detach(), z.detach(), ld.detach())
         return loss
     # per (height row, time) position and layer: 3x3 conv 2 x 64 x 128 x 9, conditioning 2 x 80 x 128, W_o 2 x 64 x 128; 8 flows x 8 layers;
     # 63 of an item's 64 rows are WN2D inputs (waveflow.py:196-206)
     fwd = 8 * 8 * (2 * 64 * 128 * 9 + 2 * 80 * 128 + 2 * 64 * 128) * 63 / 64.0
-    return dict(model=model, trainer=None, sync=sync, batch=B, segment=SEG, x=x, h=h, generator=g, step=step, n_param_bytes=4 * sum(p.numel() for p in params),
+    return dict(model=model, trainer=None, sync=sync, batch=B, segment=SEG, x=x, h=h, generator=g, last=last, step=step, n_param_bytes=4 * sum(p.numel() for p in params),
                 metric="audio samples/sec (fwd+bwd) WaveFlow-64ch seg=16000",
                 workload="WaveFlow 64ch, 8 flows, n_group 64 (waveflow_LJ_speech.json), seg=16000, batch=%d per GPU, forward + NLL + backward" % B,
                 step_flop_per_sample=3.0 * fwd, gate_launches_per_step=2 * 8 * 8,
                 gate_flop_per_launch=2.0 * (9 * 64 + 80) * 128 * B * 64 * (SEG // 64), gate_what="3x3 dilated conv + mel conditioning + gate",
                 profile_prefix="_wf_")
+
+
+DUMP_BUDGET_BYTES = 64 * 1000 * 1000      # --dump-outputs: every file written, .npy headers included
+DUMP_SEED = 20250611
+
+
+def dump_outputs(outdir, wl):
+    """--dump-outputs DIR: what the timed path handed its caller in the LAST timed step, as DIR/<name>.npy in float32 -- loss, z, logdet,
+    `logged` (FlowTrainer's four logged scalars) and `grads` (every parameter gradient, flattened and concatenated in named_parameters()
+    order).  At most DUMP_BUDGET_BYTES in all: the arrays share it smallest first, and one that does not fit whole is written as a fixed,
+    seeded sample of its flattened elements in ascending position (the same positions for the same arguments), so that two builds
+    compare element for element.  Called before anything else runs a step: z / logdet / gradients are overwritten by the next one."""
+    loss, z, logdet = wl["last"]["out"]
+    arrays = [("loss", loss.reshape(1)), ("z", z), ("logdet", logdet)]
+    if wl["trainer"] is not None:
+        arrays.append(("logged", wl["trainer"].metrics))
+    grads = [p.grad.reshape(-1) for _, p in wl["model"].named_parameters() if p.grad is not None]
+    arrays.append(("grads", torch.cat(grads)))
+    os.makedirs(outdir, exist_ok=True)
+    left = DUMP_BUDGET_BYTES // 4 - 1024 * len(arrays)             # elements; 4 KB per file for the .npy header
+    report = {}
+    for j, (name, t) in enumerate(sorted(arrays, key=lambda a: a[1].numel())):
+        n, k = t.numel(), min(t.numel(), left // (len(arrays) - j))
+        if k < n:
+            rng = np.random.default_rng(DUMP_SEED)
+            pos = torch.from_numpy(np.sort(rng.choice(n, size=k, replace=False))).to(t.device)
+            a = t.reshape(-1)[pos]
+        else:
+            a = t
+        a = a.detach().float().cpu().numpy()
+        np.save(os.path.join(outdir, name + ".npy"), a)
+        left -= a.size
+        report[name] = {"shape": list(t.shape), "elements": int(n), "written": int(a.size), "sampled": bool(k < n)}
+    return {"dir": os.path.abspath(outdir), "dtype": "float32", "seed": DUMP_SEED, "arrays": report}
 
 
 def comm_report(wl, args, use_dist, world, rank, dev, dt_own, ms_per_step, barrier):
@@ -648,7 +697,13 @@ def parse_args(argv=None):
     ap.add_argument("--selftest", choices=("ok", "fail"), default=None,
                     help="launcher / rank plumbing without a GPU: the ranks form a gloo group, reduce a number and rank 0 prints a JSON "
                          "line ('fail': rank 1 exits with code 3 instead) -- what tests/test_bench_launcher_cpu.py runs")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (loss, z, logdet, logged scalars, parameter "
+                         "gradients) as DIR/<name>.npy in float32, at most 64 MB in all (larger arrays as a fixed, seeded sample)")
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 def _free_port():
@@ -791,6 +846,7 @@ def main(argv=None):
     barrier()
     dt_all = time.perf_counter() - t0
     logged = trainer.metrics_dict() if (rank == 0 and trainer is not None) else None     # (of the last TIMED step: before comm_report's un-reduced ones)
+    dumped = dump_outputs(args.dump_outputs, wl) if (rank == 0 and args.dump_outputs) else None     # (outside the timed region)
     tmax = torch.tensor([dt_all], device=dev, dtype=torch.float64)
     if use_dist:
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
@@ -901,6 +957,8 @@ def main(argv=None):
             out["logged"] = logged                     # the scalars LightModel.training_step logs (lightning.py:58-64), rank-mean, of the last timed step
         if comm is not None:
             out["comm"] = comm
+        if dumped is not None:
+            out["dump_outputs"] = dumped
         if args.model != "waveglow":
             wl["no_inverse"] = args.no_inverse
             args.no_inverse = args.no_extra = args.no_cpu = True         # the secondary legs belong to the headline workload

@@ -293,7 +293,13 @@ def train_step(cfg, params, audio, h, sigma, need_dh=False, double=False):
 # A worker is `python -m oracle.torch_cpu --worker <dir> <index>`: inputs and outputs travel as .npy / .npz files in a scratch directory.
 # Combination: with the loss normalised by B N, the full-batch gradient is sum_w (B_w / B) grad_w -- including the 1x1 convs'
 # W^-T (sum_b dlogdet_b) T term, which is -T / N in every share -- and the loss the same weighted mean.
+# At most MAX_WORKERS worker processes run at once.  A worker never opens the device, but importing torch maps its ROCm libraries (the
+# HIP and HSA runtimes), and a shared GPU host may count such processes next to the caller that holds the GPU (a GPU test, bench.py)
+# against a limit of six per job: the caller + 5 workers.  More threads per worker take up the cores fewer workers leave free.
 # ------------------------------------------------------------------------------------------------------------------------------
+MAX_WORKERS = 5
+
+
 def _scratch():
     import tempfile
     base = "/dev/shm" if __import__("os").path.isdir("/dev/shm") else None
@@ -367,13 +373,13 @@ def _wait(procs, what):
 
 
 def _shares(B, workers):
-    workers = max(1, min(int(workers), B))
+    workers = max(1, min(int(workers), B, MAX_WORKERS))
     cut = [round(i * B / workers) for i in range(workers + 1)]
     return [(cut[i], cut[i + 1]) for i in range(workers) if cut[i + 1] > cut[i]]
 
 
 def train_step_parallel(cfg, params, audio, h, sigma, workers, threads=8, need_dh=False, double=False):
-    """train_step (or, with cfg['model'] == 'waveflow', waveflow_train_step) over the batch cut into `workers` shares, one process each
+    """train_step (or, with cfg['model'] == 'waveflow', waveflow_train_step) over the batch cut into `workers` shares (at most MAX_WORKERS), one process each
     (see above).  Same return value as train_step (arrays in float64 when double)."""
     import os
     import shutil
@@ -406,14 +412,14 @@ def train_step_parallel(cfg, params, audio, h, sigma, workers, threads=8, need_d
 
 
 def time_parallel(cfg, params, audio, h, sigma, workers, threads=8, runs=3):
-    """All-core throughput: `workers` processes, each with ONE segment (row i % B of `audio`), 1 warm-up step, then -- all released
+    """All-core throughput: `workers` processes (at most MAX_WORKERS), each with ONE segment (row i % B of `audio`), 1 warm-up step, then -- all released
     together -- `runs` timed steps.  Returns dict(samples_per_s = workers * runs * N / (last end - first start), per-worker medians)."""
     import json
     import os
     import shutil
     import time
     B, N = audio.shape
-    shares = [(i % B, i % B + 1) for i in range(int(workers))]
+    shares = [(i % B, i % B + 1) for i in range(max(1, min(int(workers), MAX_WORKERS)))]
     workdir = _scratch()
     try:
         _write_job(workdir, cfg, params, audio, h, sigma, shares, threads, False, False, runs)

@@ -130,3 +130,37 @@ def test_launch_site_names_match_rocprof_names_by_prefix(tmp_path, monkeypatch):
     assert full == "convgemm16g_kernel<8>(ConvGemm16sArgs) + gate_finish16g_kernel"
     assert bench.site_traffic("convgemm16g_kernel<WGG_EPI_PART> + gate_finish16g_kernel")[0] is None      # (the WaveGlow summary holds neither)
     assert bench.site_traffic("convlayer16g_kernel")[0] == 4.1e8
+
+
+def test_dump_outputs_writes_the_last_step_within_the_budget(tmp_path, monkeypatch):
+    """--dump-outputs: loss, z, logdet, the logged scalars and every gradient as float32 .npy files; an array that does not fit in the
+    byte budget is a seeded sample of its flattened elements, the same positions on every call."""
+    import importlib.util
+    import types
+    import numpy as np
+    import torch
+    spec = importlib.util.spec_from_file_location("bench_under_test", BENCH)
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 200_000)
+    model = torch.nn.Sequential(torch.nn.Linear(200, 300), torch.nn.Linear(300, 8))
+    model(torch.randn(4, 200)).square().sum().backward()
+    z, logdet = torch.randn(3, 1000), torch.randn(3)
+    wl = dict(model=model, trainer=types.SimpleNamespace(metrics=torch.arange(4.0)),
+              last={"out": (torch.tensor(1.5), z, logdet)})
+    rep = bench.dump_outputs(str(tmp_path / "a"), wl)
+    assert rep["arrays"]["grads"]["sampled"] and not rep["arrays"]["z"]["sampled"]
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == ["grads.npy", "logdet.npy", "logged.npy", "loss.npy", "z.npy"]
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) <= 200_000
+    got = {f[:-4]: np.load(tmp_path / "a" / f) for f in files}
+    assert all(a.dtype == np.float32 for a in got.values())
+    assert got["loss"].tolist() == [1.5] and np.array_equal(got["z"], z.numpy()) and np.array_equal(got["logdet"], logdet.numpy())
+    assert got["logged"].tolist() == [0.0, 1.0, 2.0, 3.0]
+    flat = torch.cat([p.grad.reshape(-1) for _, p in model.named_parameters()]).numpy()
+    k = rep["arrays"]["grads"]["written"]
+    assert got["grads"].size == k < flat.size
+    pos = np.sort(np.random.default_rng(bench.DUMP_SEED).choice(flat.size, k, replace=False))
+    assert np.array_equal(got["grads"], flat[pos])                  # ascending fixed positions over named_parameters() order
+    bench.dump_outputs(str(tmp_path / "b"), wl)
+    assert np.array_equal(np.load(tmp_path / "b" / "grads.npy"), got["grads"])       # fixed positions: two runs compare element for element

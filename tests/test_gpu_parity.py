@@ -21,12 +21,37 @@ pytestmark = pytest.mark.gpu
 Z_ATOL, LOSS_ATOL, GRAD_RTOL = 1e-4, 1e-6, 1e-4
 
 
-@pytest.fixture(params=["f32", "bf16x3", "bf16x3p"], autouse=True)
+PRECISIONS = ["f32", "bf16x3", "bf16x3p"]
+
+
+@pytest.fixture(params=PRECISIONS, autouse=True)
 def precision(request, monkeypatch):
     """Every parity test runs in the three arithmetic modes of the contraction kernels (include/wgflow.h WG_PREC_*):
     exact fp32 MFMA, bf16x3 split on the fly, bf16x3 from pre-split S-planes (the default).  Same tolerances for all."""
     monkeypatch.setenv("WG_PRECISION", request.param)
     return request.param
+
+
+SPLANE = "bf16x3p"          # the default arithmetic: the only mode with S-plane operands, so the only one with the kernels built on them
+_ORACLE = {"test": None, "runs": {}}
+
+
+def oracle_once(request, run):
+    """A CPU oracle run does not depend on the GPU's arithmetic mode: a test with a long oracle run computes it for the first of its three
+    modes and reuses it for the other two.  Keyed by the test function and every parameter of the case but `precision`; a run is dropped
+    once all three modes have taken it, and everything when another test function asks."""
+    test = request.node.originalname
+    params = getattr(request.node, "callspec", None)
+    key = tuple(sorted((k, repr(v)) for k, v in (params.params.items() if params else ()) if k != "precision"))
+    if _ORACLE["test"] != test:
+        _ORACLE["test"], _ORACLE["runs"] = test, {}
+    if key not in _ORACLE["runs"]:
+        _ORACLE["runs"][key] = [run(), 0]
+    entry = _ORACLE["runs"][key]
+    entry[1] += 1
+    if entry[1] == len(PRECISIONS):
+        del _ORACLE["runs"][key]
+    return entry[0]
 
 
 @pytest.fixture(scope="module")
@@ -72,6 +97,12 @@ def _check_summary(gold, m, specs, z, logdet, loss, N):
         assert np.abs(g.ravel()[:nh] - gold["grad_head"][i][:nh]).max() / max(float(gold["grad_max"][i]), 1e-30) < GRAD_RTOL, n
         gn = float(np.sqrt((g.astype(np.float64) ** 2).sum()))
         assert abs(gn - float(gold["grad_norm"][i])) <= 1e-4 * float(gold["grad_norm"][i]) + 1e-12, n
+
+
+def _coupling_oracle(wn, specs, P, x, y, gz, gls):
+    """(z, log_s, backward dict) of one coupling block from the C oracle"""
+    z_ref, ls_ref = orc.coupling_apply(wn, fill.table(specs, P), x, y)
+    return z_ref, ls_ref, orc.coupling_backward(wn, fill.table(specs, P), z_ref, y, gz, gls)
 
 
 def build(name, dev, mem_eff=True, reverse_mode=False):
@@ -167,9 +198,8 @@ def test_start_conv_folded_into_the_first_layer_vs_conv_over_h0(dev, precision, 
     """WN.start has rank ic, so the first layer's dilated conv runs over xa through the composed weight W_0[kt] W_start (csrc/wgflow.hip
     start_fold_on, wg_small.h start_fold_kernel; model/waveglow.py:99, 41-43) -- by default, i.e. in every other parity test.  Here the
     same step with the fold switched off (WG_START_FOLD=0: the conv over h_0): both against the float64 oracle, the two against each other
-    far inside the bars, and NOT bit for bit (the switch must reach the kernels)."""
-    if precision != "bf16x3p":
-        pytest.skip("the fold exists in the S-plane mode only")
+    far inside the bars, and NOT bit for bit (the switch must reach the kernels).  The fold exists in the S-plane mode only: in the other
+    two modes the switch must change nothing, bit for bit."""
     m, cfg, specs, P = build(name, dev)
     _, N, F = fill.SHAPES[name]
     B = 5
@@ -195,7 +225,7 @@ def test_start_conv_folded_into_the_first_layer_vs_conv_over_h0(dev, precision, 
         got[sw] = (z.detach().clone(), {n: q.grad.clone() for n, q in named.items()})
     z1, g1 = got["1"]
     z0, g0 = got["0"]
-    assert float((z1 - z0).abs().max()) < 2e-5 and not torch.equal(z1, z0)
+    assert float((z1 - z0).abs().max()) < 2e-5 and torch.equal(z1, z0) == (precision != SPLANE)
     for n in g1:
         assert relmax(npy(g1[n]), npy(g0[n])) < 2e-5, n
 
@@ -352,8 +382,7 @@ def test_noncausal_layer_alone_vs_reference_golden(dev, golden_dir, precision, c
     """NonCausalLayer.forward on its own (model/waveglow.py:18-46, 41-46) through wg_layer_apply: against the reference's own output
     (block_layer.npz) and a plain torch fp32 evaluation of the same formulas; weight norm on and off, the last-layer form (no residual),
     a dilation that is not a power of two and radix 5."""
-    if precision != "f32":
-        pytest.skip("the stand-alone layer always runs the exact-fp32 kernels")
+    # (the stand-alone layer runs the exact-fp32 kernels whatever WG_PRECISION says: the same bars in every mode)
     import torch.nn.functional as Fn
     from make_golden import LAYER_CASES, layer_inputs
     C, Cd, Cs, radix, dil, last, wn, B, Tn = LAYER_CASES[cname]
@@ -390,8 +419,7 @@ def test_noncausal_layer_alone_vs_reference_golden(dev, golden_dir, precision, c
 def test_noncausal_layer2d_alone_vs_reference_golden(dev, golden_dir, precision, cname):
     """NonCausalLayer2D.forward on its own (model/waveflow.py:14-51): the 3x3 conv dilated (h_dilation, dilation), causal along the height
     axis, as nine K segments with plane-row offsets; against the reference's own output (block_layer.npz, keys 2d_*)."""
-    if precision != "f32":
-        pytest.skip("the stand-alone layer always runs the exact-fp32 kernels")
+    # (the stand-alone layer runs the exact-fp32 kernels whatever WG_PRECISION says: the same bars in every mode)
     from make_golden import LAYER2D_CASES, layer2d_inputs
     C, Cd, Cs, hd, dil, last, wn, B, H, W = LAYER2D_CASES[cname]
     P, x, y = layer2d_inputs(cname)
@@ -439,8 +467,7 @@ def test_noncausal_layer_alone_is_differentiable_vs_reference_golden(dev, golden
     """NonCausalLayer is an ordinary differentiable module upstream (model/waveglow.py:18-46): `res, skip = layer(x, y)` followed by any
     loss gives gradients for x, y, W and W_o (g and v under weight norm).  Here the call is an autograd node (engine.LayerFn) whose
     backward is wg_layer_backward; every gradient against what the reference's own autograd gave (block_layer.npz)."""
-    if precision != "f32":
-        pytest.skip("the stand-alone layer always runs the exact-fp32 kernels")
+    # (the stand-alone layer runs the exact-fp32 kernels whatever WG_PRECISION says: the same bars in every mode)
     from make_golden import LAYER_CASES, layer_inputs
     C, Cd, Cs, radix, dil, last, wn, B, Tn = LAYER_CASES[cname]
     P, x, y = layer_inputs(cname)
@@ -458,8 +485,7 @@ def test_noncausal_layer_alone_is_differentiable_vs_reference_golden(dev, golden
 def test_noncausal_layer2d_alone_is_differentiable_vs_reference_golden(dev, golden_dir, precision, cname):
     """The same for NonCausalLayer2D (model/waveflow.py:14-51): nine taps with plane-row offsets in the weight gradient and the data
     gradient, d y summed over the height axis the conditioning was broadcast over."""
-    if precision != "f32":
-        pytest.skip("the stand-alone layer always runs the exact-fp32 kernels")
+    # (the stand-alone layer runs the exact-fp32 kernels whatever WG_PRECISION says: the same bars in every mode)
     from make_golden import LAYER2D_CASES, layer2d_inputs
     C, Cd, Cs, hd, dil, last, wn, B, H, W = LAYER2D_CASES[cname]
     P, x, y = layer2d_inputs(cname)
@@ -479,8 +505,7 @@ def test_noncausal_layer_alone_with_biases_vs_torch(dev, precision, cname):
     the flag): xy = W(x) + b_W + y and W_o(z) + b_o, so the biases are constants on y and on the outputs around wg_layer_apply, and their
     gradients are sums of d y / of the output gradients.  Outputs and every gradient (x, y, the weights, both biases) against a float64
     torch evaluation of the reference's formulas on the CPU, with and without autograd."""
-    if precision != "f32":
-        pytest.skip("the stand-alone layer always runs the exact-fp32 kernels")
+    # (the stand-alone layer runs the exact-fp32 kernels whatever WG_PRECISION says: the same bars in every mode)
     import torch.nn.functional as Fn
     from make_golden import LAYER2D_CASES, LAYER_CASES, layer2d_inputs, layer_inputs
     two_d = cname.startswith("2d_")
@@ -535,9 +560,8 @@ def test_one_launch_layer_vs_two_launches(dev, precision, monkeypatch, name):
     """convlayer16h_kernel (wg_layer16h.h): one launch per WN layer -- gate conv -> gate -> W_o -> residual / skip, model/waveglow.py:41-46 --
     wherever both products are small-grid launches (single-utterance synthesis).  The gate crosses workgroups inside the launch (sc1
     stores, an arrival counter per column tile, sc1 loads); the arithmetic is the two launches' own, so forward and inverse must agree with
-    the two-launch path (WG_LAYER_FUSION=0) to rounding, repeat bit for bit, and the launch counter must show that the fused kernel ran."""
-    if precision != "bf16x3p":
-        pytest.skip("the one-launch layer exists in the S-plane mode only")
+    the two-launch path (WG_LAYER_FUSION=0) to rounding, repeat bit for bit, and the launch counter must show that the fused kernel ran.
+    The kernel exists in the S-plane mode only: in the other two modes the counter must stay at zero with the switch on."""
     from constant_memory_waveglow_amd import _lib
     m, cfg, specs, P = build(name, dev)
     _, N, F = fill.SHAPES[name]
@@ -557,7 +581,7 @@ def test_one_launch_layer_vs_two_launches(dev, precision, monkeypatch, name):
                 runs.append((z, ld, xr, ldr))
         torch.cuda.synchronize()
         n = _lib.lib().wg_stat_layer_launches() - before
-        assert n == (4 * 2 * cfg["flows"] * depth if fused == "1" else 0), n
+        assert n == (4 * 2 * cfg["flows"] * depth if fused == "1" and precision == SPLANE else 0), n
         for later in runs[1:]:                                    # a hand-off that read stale bytes would not repeat bit for bit
             for a, b in zip(runs[0], later):
                 assert torch.equal(a, b)
@@ -577,9 +601,8 @@ def test_layer_launch_of_the_training_shapes_vs_two_launches(dev, precision, mon
     chip in whole rounds of 256 x 128 tiles (batch 16: two rounds, batch 24: three -- the headline shape).  The gate crosses workgroups
     inside the launch (write-through stores, an arrival counter per column tile published half a tile late, sc1 loads).  A whole training
     step -- forward, recompute, backward -- must agree with the two-launch path (WG_LAYER_FUSION_BIG=0) to rounding, repeat bit for bit,
-    and the launch counter must show the fused kernel ran in the forward and in the recompute pass of every flow."""
-    if precision != "bf16x3p":
-        pytest.skip("the one-launch layer exists in the S-plane mode only")
+    and the launch counter must show the fused kernel ran in the forward and in the recompute pass of every flow (S-plane mode; the other
+    two modes have no such kernel, and the counter must stay at zero)."""
     from constant_memory_waveglow_amd import _lib
     from constant_memory_waveglow_amd.parallel import FlowTrainer
     m, cfg, specs, P = build("c2", dev)
@@ -599,7 +622,7 @@ def test_layer_launch_of_the_training_shapes_vs_two_launches(dev, precision, mon
         torch.cuda.synchronize()
         n = _lib.lib().wg_stat_layer_launches() - before
         # per step: 7 of 8 layers of every flow in the forward, and in the recompute of every flow but the one the forward kept
-        assert n == (3 * (cfg["flows"] * 7 + (cfg["flows"] - 1) * 7) if fused == "1" else 0), n
+        assert n == (3 * (cfg["flows"] * 7 + (cfg["flows"] - 1) * 7) if fused == "1" and precision == SPLANE else 0), n
         for later in runs[1:]:
             for a, b in zip(runs[0], later):
                 assert torch.equal(a, b)
@@ -612,29 +635,25 @@ def test_layer_launch_of_the_training_shapes_vs_two_launches(dev, precision, mon
         assert float((g1[s:e] - g0[s:e]).abs().max()) <= 1e-5 * float(g0[s:e].abs().max()), b
 
 
-def test_c2_full_batch_vs_oracle(dev, precision):
+def test_c2_full_batch_vs_oracle(dev, precision, request):
     """The HEADLINE shape itself -- BASELINE.json configs[1]: 256 channels, 12 flows, batch 24 x 16000 samples
     (configs/waveglow_LJ_speech.json:6-29), 48 000 columns per launch: wgrad16t's two-phase plan at K = 48 000, the 750-tile persistent
     walks, XCD rows, the one-product skip / conditioning gradient -- through FlowTrainer.step (wg_train_step, what bench.py times)
     against the float64 torch-CPU oracle (oracle/torch_cpu.py, pinned to the reference's goldens by tests/test_oracle_golden.py).
     Batch items are independent, so the oracle runs as one worker process per share of the batch (train_step_parallel).
     Bars: z 1e-4, logdet rtol 1e-4, loss 1e-6, every one of the 459 gradients and dh (from the same call: FlowTrainer.want_dh) within
-    1e-4 of its tensor's max; then the same for memory_efficient=False, the other benchmarked form, against the same oracle run."""
-    if precision != "bf16x3p":
-        pytest.skip("the headline shape is checked in the default arithmetic (CPU oracle time)")
+    1e-4 of its tensor's max; then the same for memory_efficient=False, the other benchmarked form, against the same oracle run.
+    In all three arithmetic modes, against one oracle run."""
     from oracle import torch_cpu
     from constant_memory_waveglow_amd.parallel import FlowTrainer
     m, cfg, specs, P = build("c2", dev)
     B, N, F = 24, 16000, 63
     audio, h = fill.inputs("c2full", B, N, F, cfg["n_mels"])
-    try:
-        import psutil
-        cores = psutil.cpu_count(logical=False) or os.cpu_count() or 8
-    except Exception:                                            # noqa: BLE001
-        cores = os.cpu_count() or 8
-    workers = max(1, min(B, cores // 8))
-    ref = torch_cpu.train_step_parallel(cfg, fill.table(specs, P), audio, h, fill.SIGMA, workers=workers, threads=max(1, min(8, cores // workers)),
-                                        need_dh=True, double=True)
+    n_allowed, quota, firsts = torch_cpu.host_cpu_budget()      # (what this process may really use: a container may grant a fraction of what it shows)
+    cores = max(1, int(quota) if quota else len(firsts))
+    workers = max(1, min(B, cores // 2, torch_cpu.MAX_WORKERS))
+    ref = oracle_once(request, lambda: torch_cpu.train_step_parallel(
+        cfg, fill.table(specs, P), audio, h, fill.SIGMA, workers=workers, threads=max(1, min(8, cores // workers)), need_dh=True, double=True))
     x, ht = T(audio, dev), T(h, dev)
     # (model_c2_full.npz: one training step of the REFERENCE at this size on the CPU -- fp32, so looser than the float64 oracle, but the
     # reference itself: a summary of z, logdet, loss, every gradient's norm / head, dh; tests/golden/make_golden.py c2_full)
@@ -651,8 +670,10 @@ def test_c2_full_batch_vs_oracle(dev, precision):
         parts0 = cm._lib.lib().wg_stat_gate_part_launches()
         loss, z, logdet = tr.step(x, ht)
         # the timed shape runs the rank-2ic form of the skip path with the gate convs writing their share of `out`: 8 per WN pass --
-        # 12 forward + 11 recompute passes in the constant-memory form, 12 forward passes with stored activations
-        assert cm._lib.lib().wg_stat_gate_part_launches() - parts0 == 8 * (23 if mem_eff else 12)
+        # 12 forward + 11 recompute passes in the constant-memory form, 12 forward passes with stored activations (S-plane mode: the
+        # other two modes have no S-plane gate output, so no such launch)
+        parts = 8 * (23 if mem_eff else 12) if precision == SPLANE else 0
+        assert cm._lib.lib().wg_stat_gate_part_launches() - parts0 == parts
         assert np.abs(npy(z) - ref["z"]).max() < Z_ATOL
         assert logdet_close(npy(logdet), ref["logdet"], N)
         assert abs(float(loss) - ref["loss"]) < LOSS_ATOL
@@ -926,9 +947,8 @@ def test_coupling_block_with_any_transform_under_autocast(dev, mem_eff):
 def test_coupling_block_on_shared_b_tiles_vs_oracle(dev, precision):
     """One coupling block at the shipped WN width (256 channels, so the gate conv has 512 rows) on 2 x 16 384 columns: 1 024 gate-conv
     tiles = 2 per CU, the shape at which the engine runs the 256 x 128 form of the conv kernel (two compute groups sharing one B image,
-    convgemm16q_kernel<.., MG = 2>) -- checked against the oracle, forward and backward."""
-    if precision != "bf16x3p":
-        pytest.skip("the shared-B tile exists in the S-plane mode only")
+    convgemm16q_kernel<.., MG = 2>) -- checked against the oracle, forward and backward.  (That form exists in the S-plane mode only; the
+    other two modes are held to the same bars on their own kernels at this shape.)"""
     wn = dict(in_channels=4, aux_channels=80, residual_channels=256, dilation_channels=256, skip_channels=256, depth=2, radix=3)
     specs = fill.wn_param_specs("F.", 4, 80, 256, 256, 256, 2, 3)
     tag = "coupling/mg2"
@@ -957,14 +977,13 @@ def test_coupling_block_on_shared_b_tiles_vs_oracle(dev, precision):
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("B,Tn,want_store", [(12, 2000, False), (1, 24400, False), (24, 2000, True)])
-def test_coupling_block_on_flattened_column_tiles_vs_oracle(dev, precision, B, Tn, want_store):
+def test_coupling_block_on_flattened_column_tiles_vs_oracle(dev, precision, request, B, Tn, want_store):
     """convgemm16g_kernel (csrc/wg_gemm16g.h): 256 x 192 tiles over the FLATTENED (plane row, time) columns, eight multiplying waves fed by
     LDS-DMA.  One coupling block at the shipped WN (256 channels, depth 8: halo 128) against the oracle, forward and backward, at shapes
     that put the tile seams everywhere: 12 x 2048 padded columns = 128 column tiles that straddle plane rows (2048 = 10.67 tiles); one
     plane row of 24 400 steps whose last column tile is partial; 24 x 2000, the headline columns, where the 256-row data-gradient conv
-    runs on the kernel as well (one tile per CU).  The library names the instantiation every timed launch ran (wg_timer_read_name)."""
-    if precision != "bf16x3p":
-        pytest.skip("the LDS-DMA kernel exists in the S-plane mode only")
+    runs on the kernel as well (one tile per CU).  The library names the instantiation every timed launch ran (wg_timer_read_name).  The
+    LDS-DMA kernels exist in the S-plane mode only: in the other two modes none of them may run, and the same bars hold."""
     import ctypes as C
     from constant_memory_waveglow_amd import _lib
     wn = dict(in_channels=4, aux_channels=80, residual_channels=256, dilation_channels=256, skip_channels=256, depth=8, radix=3)
@@ -975,8 +994,7 @@ def test_coupling_block_on_flattened_column_tiles_vs_oracle(dev, precision, B, T
     y = fill.normal(tag + "/y", (B, 80, Tn))
     gz = fill.normal(tag + "/gz", x.shape)
     gls = fill.normal(tag + "/gls", (B, 4, Tn))
-    z_ref, ls_ref = orc.coupling_apply(wn, fill.table(specs, P), x, y)
-    ref = orc.coupling_backward(wn, fill.table(specs, P), z_ref, y, gz, gls)
+    z_ref, ls_ref, ref = oracle_once(request, lambda: _coupling_oracle(wn, specs, P, x, y, gz, gls))
     blk = cm.AffineCouplingBlock(cm.WN, True, zero_init=False, **wn)
     blk.load_state_dict({n: torch.from_numpy(v) for n, v in P.items()})
     blk = blk.to(dev)
@@ -1003,12 +1021,14 @@ def test_coupling_block_on_flattened_column_tiles_vs_oracle(dev, precision, B, T
     gate = {k[1]: v for k, v in sites.items() if k[0] == _lib.K_CONV_GATE}
     layer = sum(v for k, v in sites.items() if k[0] == _lib.K_LAYER and k[1] == "convlayer16g_kernel")
     # (the first layer's gate conv reads xa through the composed weight -- start_fold_on: 6 chunks of K -- and takes a 16x16x32 kernel)
-    if want_store:          # 256 column tiles, one per CU: layers 1-6 of 8 run gate conv + residual product as ONE launch (convlayer16g_kernel)
+    if precision != SPLANE:
+        assert not any(k[1].startswith(("convgemm16g_kernel", "convlayer16g_kernel")) for k in sites), sites
+    elif want_store:          # 256 column tiles, one per CU: layers 1-6 of 8 run gate conv + residual product as ONE launch (convlayer16g_kernel)
         assert layer == 12 and gate.get("convgemm16g_kernel<EPI_GATE_SO>", 0) == 2 and sum(gate.values()) == 4, sites
     else:                   # layers 1-7 of 8, forward + the backward's recompute
         assert layer == 0 and gate.get("convgemm16g_kernel<EPI_GATE_SO>", 0) == 14 and sum(gate.values()) == 16, sites
     store = sum(v for k, v in sites.items() if k[0] == _lib.K_CONV_STORE and k[1] == "convgemm16g_kernel<EPI_STORE_SO>")
-    assert (store >= 8) == want_store, sites                                     # the 8 data-gradient convs (K = 1536) of the backward
+    assert (store >= 8) == (want_store and precision == SPLANE), sites           # the 8 data-gradient convs (K = 1536) of the backward
     assert np.abs(npy(z) - z_ref).max() < 1e-5 and np.abs(npy(ls) - ls_ref).max() < 1e-5
     got = dict(dx=npy(xt.grad), dy=npy(yt.grad))
     assert relmax(got["dx"], ref["dx"]) < GRAD_RTOL and relmax(got["dy"], ref["dy"]) < GRAD_RTOL
@@ -1022,9 +1042,8 @@ def test_layer_as_one_launch_on_flattened_tiles_vs_two_launches(dev, precision, 
     """convlayer16g_kernel (csrc/wg_gemm16g.h): a layer's gate conv and residual product in ONE launch -- a workgroup owns whole 192-column
     tiles, computes both 256-row gate tiles and then, from its own stores, the residual product.  A whole training step at the headline
     columns (24 x 2000) must agree with the two-launch path (WG_LAYER_G=0) to rounding and repeat bit for bit, and the counter must show
-    the kernel ran: 6 of 8 layers of every flow in the forward and in the recompute of every flow but the one the forward kept."""
-    if precision != "bf16x3p":
-        pytest.skip("the LDS-DMA kernels exist in the S-plane mode only")
+    the kernel ran: 6 of 8 layers of every flow in the forward and in the recompute of every flow but the one the forward kept (S-plane
+    mode; the other two modes have no such kernel, and the counter must stay at zero)."""
     from constant_memory_waveglow_amd import _lib
     from constant_memory_waveglow_amd.parallel import FlowTrainer
     m, cfg, specs, P = build("c2", dev)
@@ -1045,7 +1064,7 @@ def test_layer_as_one_launch_on_flattened_tiles_vs_two_launches(dev, precision, 
         n = _lib.lib().wg_stat_layerg_launches() - before
         # (6 of 8 layers: the last has no residual product, the first -- WN.start folded into its weight, start_fold_on -- is a gate product of
         # 6 chunks and takes the 16x16x32 kernel + its own residual launch)
-        assert n == (2 * (cfg["flows"] * 6 + (cfg["flows"] - 1) * 6) if fused == "1" else 0), n
+        assert n == (2 * (cfg["flows"] * 6 + (cfg["flows"] - 1) * 6) if fused == "1" and precision == SPLANE else 0), n
         for a, b in zip(runs[0], runs[1]):
             assert torch.equal(a, b)
         res[fused] = runs[0]
@@ -1059,9 +1078,8 @@ def test_layer_as_one_launch_on_flattened_tiles_vs_two_launches(dev, precision, 
 def test_inverse_seam_launch_vs_three_launches(dev, precision, monkeypatch):
     """Synthesis between two WNs: the inverse affine, the inverse 1x1 conv and the next WN's start conv as ONE launch
     (end_affine_kernel<8, true>, opt-in WG_INV_SEAM=1: measured no faster, csrc/wgflow.hip run_inv_seam) against the three launches: the
-    same expressions in the same order, so x must be equal bit for bit (logdet: the per-block sums of log_s are added in another order)."""
-    if precision != "bf16x3p":
-        pytest.skip("the seam kernel writes S-planes: the default arithmetic only")
+    same expressions in the same order, so x must be equal bit for bit (logdet: the per-block sums of log_s are added in another order).
+    The seam kernel writes S-planes: in the other two modes the switch must leave the three launches' result as it is."""
     m, cfg, specs, P = build("c2", dev)
     for B, F in ((1, 63), (3, 20)):
         h = T(fill.normal("seam/h%d" % B, (B, cfg["n_mels"], F)), dev)
@@ -1330,9 +1348,8 @@ def test_wsrglow_timed_workload_vs_reference_golden(dev, golden_dir, precision, 
     49 152 low-rate samples and 55 296 STFT bins are quantised on the way in; a decision whose pre-rounding value sits within float noise of
     a bin edge may fall the other way on the GPU (here: ONE phase bin of item 0, frame 438).  The test finds such decisions from the
     recorded indices, allows two, and hands the flow the reference's table rows at those frames -- what is compared is then the same function
-    -- skipping only the table-gradient rows the differing decisions themselves route to."""
-    if precision != "bf16x3p":
-        pytest.skip("the timed workload runs in the default arithmetic")
+    -- skipping only the table-gradient rows the differing decisions themselves route to.  In all three arithmetic modes (the cut gate
+    conv is an S-plane kernel: its counter stays at zero in the other two)."""
     from constant_memory_waveglow_amd import _lib, engine
     from constant_memory_waveglow_amd.parallel import FlowTrainer
     name = "wsr_full"
@@ -1398,7 +1415,7 @@ def test_wsrglow_timed_workload_vs_reference_golden(dev, golden_dir, precision, 
     before = _lib.lib().wg_stat_gate_split_launches()
     loss, z, logdet = tr.step(T(audio, dev), T(c, dev))
     torch.cuda.synchronize()
-    assert _lib.lib().wg_stat_gate_split_launches() - before == (2 * len(m.WNs) - 1) * 8
+    assert _lib.lib().wg_stat_gate_split_launches() - before == ((2 * len(m.WNs) - 1) * 8 if precision == SPLANE else 0)
     zz = npy(z)
     assert np.abs(zz[:, :256] - gold["z_head"]).max() < Z_ATOL and np.abs(zz[:, -256:] - gold["z_tail"]).max() < Z_ATOL
     zn = np.sqrt((zz.astype(np.float64) ** 2).sum(1))
@@ -1417,11 +1434,10 @@ def test_wsrglow_timed_workload_vs_reference_golden(dev, golden_dir, precision, 
         assert relmax(npy(named[n].grad)[keep], gold["grad::" + n][keep]) < GRAD_RTOL, n
 
 
-def test_wsrglow_full_width_vs_oracle(dev, precision):
+def test_wsrglow_full_width_vs_oracle(dev, precision, request):
     """The shipped WSRGlow width (WN 256 channels x 8 layers, 229.7 M parameters, V = 3659 -> 4096 per flow) on one short segment
-    against the oracle: the conditioning GEMM segment with K = 3659 is the shape the small fixtures do not reach."""
-    if precision != "bf16x3p":
-        pytest.skip("full-width case runs in the default arithmetic only (CPU oracle time)")
+    against the oracle: the conditioning GEMM segment with K = 3659 is the shape the small fixtures do not reach.  All three arithmetic
+    modes against one oracle run."""
     name = "wsr_full"
     cfg = dict(fill.CONFIGS["wsr"], dilation_channels=256, residual_channels=256, skip_channels=256, depth=8)
     B, N = 1, 1024
@@ -1429,9 +1445,12 @@ def test_wsrglow_full_width_vs_oracle(dev, precision):
     P = fill.fill_params(specs, name + "/")
     tabs = fill.wsr_tables(name + "/")
     audio, c = fill.wsr_inputs(name, B, N)
-    cond = orc.wsr_cond(c, tabs["mu_enc.1.weight"], tabs["angle_embed.embed.weight"])
-    ref = orc.train_step(orc.make_config(**cfg), fill.table(specs, P), audio, cond, 1.0, need_dh=True)
-    dmu_ref, dang_ref = orc.wsr_cond_backward(c, ref["dh"])
+
+    def run_oracle():
+        cond = orc.wsr_cond(c, tabs["mu_enc.1.weight"], tabs["angle_embed.embed.weight"])
+        ref = orc.train_step(orc.make_config(**cfg), fill.table(specs, P), audio, cond, 1.0, need_dh=True)
+        return ref, orc.wsr_cond_backward(c, ref["dh"])
+    ref, (dmu_ref, dang_ref) = oracle_once(request, run_oracle)
     m = cm.WSRGlow(upsample_rate=2, memory_efficient=True, bias=False)
     sd = {k: torch.from_numpy(v) for k, v in P.items()}
     sd.update({k: torch.from_numpy(v) for k, v in tabs.items()})
@@ -1455,8 +1474,7 @@ def test_wsrglow_full_width_vs_oracle(dev, precision):
 
 @pytest.mark.parametrize("wd,betas", [(0.0, (0.9, 0.999)), (0.01, (0.9, 0.98))])
 def test_flat_adam_matches_torch_adam(dev, precision, wd, betas):
-    if precision != "bf16x3p":
-        pytest.skip("optimizer arithmetic does not depend on the contraction mode")
+    # (the optimizer's arithmetic does not depend on the contraction mode: the same check in every mode)
     from constant_memory_waveglow_amd.parallel import FlowTrainer, FlatAdam
     m, cfg, specs, P = build("micro", dev)
     B, N, F = fill.SHAPES["micro"]
@@ -1693,8 +1711,7 @@ def test_waveflow_timed_workload_vs_reference_golden(dev, golden_dir, precision)
     """`bench.py --model waveflow` at its own size -- configs/waveflow_LJ_speech.json: 8 flows, 64 rows, 64 channels, batch 12 x 16000 --
     against one training step of the reference itself on the CPU (model_wf_full.npz, a summary: both ends and the per-item norm of z,
     logdet, loss, norm / head of every gradient, d mel in full)."""
-    if precision != "bf16x3p":
-        pytest.skip("the timed workload runs in the default arithmetic")
+    # (in all three arithmetic modes)
     cfg = dict(flows=8, n_group=64, n_mels=80, dilation_channels=64, residual_channels=64, skip_channels=64)
     B, N, F = 12, 16000, 63
     specs = fill.waveflow_param_specs(cfg)
@@ -1712,14 +1729,13 @@ def test_waveflow_timed_workload_vs_reference_golden(dev, golden_dir, precision)
     assert relmax(npy(ht.grad), gold["dmel"]) < GRAD_RTOL
 
 
-def test_waveflow_timed_workload_vs_float64_oracle(dev, precision):
+def test_waveflow_timed_workload_vs_float64_oracle(dev, precision, request):
     """`bench.py --model waveflow` at its own size (configs/waveflow_LJ_speech.json: 8 flows, 64 rows, 64 channels, batch 12 x 16000) against
     the float64 torch-CPU oracle IN FULL -- every element of z, logdet, loss, d loss / d mel and every one of the 299 gradients -- where the
     reference's own step at this size is kept as a summary only (test_waveflow_timed_workload_vs_reference_golden).  The oracle
     (oracle/torch_cpu.waveflow_train_step, pinned to the reference's goldens by tests/test_oracle_golden.py) runs one worker process per
-    share of the batch.  Bars: z 1e-4, logdet rtol 1e-4, loss 1e-6, every gradient within 1e-4 of its tensor's max."""
-    if precision != "bf16x3p":
-        pytest.skip("the timed workload runs in the default arithmetic (CPU oracle time)")
+    share of the batch.  Bars: z 1e-4, logdet rtol 1e-4, loss 1e-6, every gradient within 1e-4 of its tensor's max.  All three arithmetic
+    modes against one oracle run."""
     from oracle import torch_cpu
     cfg = dict(flows=8, n_group=64, n_mels=80, dilation_channels=64, residual_channels=64, skip_channels=64)
     B, N, F = 12, 16000, 63
@@ -1728,9 +1744,10 @@ def test_waveflow_timed_workload_vs_float64_oracle(dev, precision):
     audio, mel = fill.waveflow_inputs("wf_full", B, N, F, 80)
     n_allowed, quota, firsts = torch_cpu.host_cpu_budget()      # (what this process may really use: a container may grant a fraction of what it shows)
     cores = max(1, int(quota) if quota else len(firsts))
-    workers = max(1, min(B, cores // 2))
-    ref = torch_cpu.train_step_parallel(dict(cfg, model="waveflow"), fill.table(specs, P), audio, mel, fill.SIGMA, workers=workers,
-                                        threads=max(1, min(4, cores // workers)), need_dh=True, double=True)
+    workers = max(1, min(B, cores // 2, torch_cpu.MAX_WORKERS))
+    ref = oracle_once(request, lambda: torch_cpu.train_step_parallel(
+        dict(cfg, model="waveflow"), fill.table(specs, P), audio, mel, fill.SIGMA, workers=workers, threads=max(1, min(4, cores // workers)),
+        need_dh=True, double=True))
     m = cm.WaveFlow(use_conv1x1=False, memory_efficient=False, bias=False, **cfg)
     m.load_state_dict({k: torch.from_numpy(v) for k, v in P.items()})
     m = m.to(dev)
@@ -1801,8 +1818,7 @@ def test_waveflow_full_size_properties(dev, precision):
 
 def test_wsrglow_full_size_properties(dev, precision):
     """BASELINE.json configs[4] at its full size (configs/wsrglow_vctk_2x.json: 229.7 M parameters, batch 12 x 8192)."""
-    if precision != "bf16x3p":
-        pytest.skip("full-size case runs in the default arithmetic only")
+    # (in all three arithmetic modes)
     torch.manual_seed(0)
     m = cm.WSRGlow(upsample_rate=2, memory_efficient=True, bias=False)
     with torch.no_grad():
@@ -1848,9 +1864,8 @@ def test_wsrglow_gate_conv_cut_along_k_vs_uncut(dev, precision, monkeypatch):
     """WSRGlow's gate conv at the timed shape (M 512, K 4432 = 139 chunks, 12 x 512 columns = 32 column tiles x 2 row tiles) fills a
     quarter of the CUs, so run_convgemm cuts K in 4 (convgemm16g_kernel<8> + gate_finish16g_kernel, csrc/wg_gemm16g.h).  The cut changes
     only the fp32 summation order: a step must agree with the uncut kernels (WG_G192_SPLITK=0) to rounding, repeat bit for bit, and
-    the counter must show the cut ran (every gate conv of the forward and of the recompute)."""
-    if precision != "bf16x3p":
-        pytest.skip("the LDS-DMA kernels exist in the S-plane mode only")
+    the counter must show the cut ran (every gate conv of the forward and of the recompute).  The cut kernels exist in the S-plane mode
+    only: in the other two modes the counter must stay at zero with the switch on."""
     from constant_memory_waveglow_amd import _lib
     from constant_memory_waveglow_amd.parallel import FlowTrainer
     torch.manual_seed(0)
@@ -1875,7 +1890,7 @@ def test_wsrglow_gate_conv_cut_along_k_vs_uncut(dev, precision, monkeypatch):
         torch.cuda.synchronize()
         n = _lib.lib().wg_stat_gate_split_launches() - before
         flows, layers = len(m.WNs), 8
-        assert n == (2 * (2 * flows - 1) * layers if cut == "1" else 0), n
+        assert n == (2 * (2 * flows - 1) * layers if cut == "1" and precision == SPLANE else 0), n
         for a, b in zip(runs[0][:3], runs[1][:3]):
             assert torch.equal(a, b)
         # (the two embedding tables' gradients go through LDS float atomics: equal to rounding; everything else repeats exactly)
@@ -1980,14 +1995,13 @@ def test_wn2d_on_its_own_is_differentiable_vs_reference_golden(dev, golden_dir, 
     assert len(order) == len(names)
 
 
-def test_waveflow_chip_filling_shape_vs_oracle(dev, precision):
+def test_waveflow_chip_filling_shape_vs_oracle(dev, precision, request):
     """The shipped WaveFlow width at a size that FILLS the chip -- batch 4 x 16000 samples = 256 plane rows x 250 columns -- against the
     C oracle: the launches the small fixtures never reach: 64-row tiles for the 64-row products (convgemm16q_kernel<.., M64>: the
     data-gradient conv, residual / skip products, gate backward), the gate conv on 128 x 256 column-group tiles (<.., CG2>), the grouped
     weight-gradient launch at K = 64 000 columns, wf_rowsum_s_kernel's four-way row split (configs/waveflow_LJ_speech.json is this
     network at batch 12)."""
-    if precision != "bf16x3p":
-        pytest.skip("the chip-filling WaveFlow case runs in the default arithmetic only (CPU oracle time)")
+    # (all three arithmetic modes against one oracle run)
     from oracle import wf_oracle as wfo
     name = "wf_chip"
     cfg = dict(flows=8, n_group=64, n_mels=80, dilation_channels=64, residual_channels=64, skip_channels=64)
@@ -1995,7 +2009,8 @@ def test_waveflow_chip_filling_shape_vs_oracle(dev, precision):
     specs = fill.waveflow_param_specs(cfg)
     P = fill.fill_params(specs, name + "/")
     audio, mel = fill.waveflow_inputs(name, B, N, F, cfg["n_mels"])
-    ref = wfo.train_step(wfo.make_config(**cfg), fill.table(specs, P), audio, mel, fill.SIGMA, need_dmel=True)
+    ref = oracle_once(request, lambda: wfo.train_step(wfo.make_config(**cfg), fill.table(specs, P), audio, mel, fill.SIGMA,
+                                                            need_dmel=True))
     m = cm.WaveFlow(use_conv1x1=False, memory_efficient=False, bias=False, **cfg)
     m.load_state_dict({k: torch.from_numpy(v) for k, v in P.items()})
     m = m.to(dev)
@@ -2020,8 +2035,7 @@ def test_waveflow_chip_filling_shape_vs_oracle(dev, precision):
 def test_melspec_kernel_vs_oracle(dev, precision, B, N):
     """wg_melspec against the numpy restatement of MelSpec (reflection pad, 1024-point periodic-Hann STFT power, HTK mel filters to
     8 kHz, log(x + 1e-7)); the configuration is the one every WaveGlow / WaveFlow config ships (conditioner.args)."""
-    if precision != "f32":
-        pytest.skip("the conditioner does not depend on the contraction mode")
+    # (the conditioner does not depend on the contraction mode: the same check in every mode)
     from oracle import mel_oracle as mo
     x = fill.uniform("mel/x%d_%d" % (B, N), (B, N), -0.8, 0.8)
     x[0, : N // 4] *= 1e-3                                       # a quiet stretch: log-mel near its floor
@@ -2039,8 +2053,7 @@ def test_melspec_kernel_vs_reference_golden(dev, golden_dir, precision, tag):
     """wg_melspec against the reference's MelSpec class run over torch.stft (tests/golden/cond_melspec.npz): the power spectrogram
     before the filterbank -- reflection pad, periodic Hann, STFT, |.|^2: all torch's own code upstream -- and the log-mel output
     (whose filterbank is the published torchaudio formula on both sides)."""
-    if precision != "f32":
-        pytest.skip("the conditioner does not depend on the contraction mode")
+    # (the conditioner does not depend on the contraction mode: the same check in every mode)
     from constant_memory_waveglow_amd import engine
     G = np.load(os.path.join(golden_dir, "cond_melspec.npz"))
     kw = fill.MEL_KW
@@ -2089,8 +2102,7 @@ def test_repeated_steps_are_bitwise_identical(dev, precision):
 @pytest.mark.parametrize("tag", list(fill.DECIMATE_CASES))
 def test_stft_decimate_vs_reference_golden(dev, golden_dir, precision, tag):
     """wg_lowpass behind STFTDecimate against the reference's own output (cond_stftdecimate.npz) and the oracle."""
-    if precision != "f32":
-        pytest.skip("the conditioner does not depend on the contraction mode")
+    # (the conditioner does not depend on the contraction mode: the same check in every mode)
     from oracle import mel_oracle as mo
     B, Tn, r = fill.DECIMATE_CASES[tag]
     x = fill.uniform("decimate/" + tag, (B, Tn), -0.9, 0.9)
@@ -2105,8 +2117,7 @@ def test_stft_decimate_vs_reference_golden(dev, golden_dir, precision, tag):
 def test_half_inference_matches_fp32_engine(dev, precision):
     """`inference.py --half` (model.half(), cond.half(), inference.py:33-36): half storage in and out, fp32 arithmetic inside.
     The result equals the fp32 run on the half-rounded weights / inputs, rounded to half."""
-    if precision != "bf16x3p":
-        pytest.skip("one arithmetic mode is enough for the dtype plumbing")
+    # (the half-storage plumbing is the same in every arithmetic mode, and checked in each)
     m, cfg, specs, P = build("micro", dev)
     B, N, F = fill.SHAPES["micro"]
     _, h = fill.inputs("micro", B, N, F, cfg["n_mels"])
@@ -2155,15 +2166,14 @@ def test_waveflow_after_remove_weight_norms(dev, precision):
                                                        (1, 64, 8, 80, 256, True), (2, 500, 3, 80, 256, True), (2, 512, 8, 1500, 256, True),
                                                        (3, 700, 5, 3659, 256, True), (2, 500, 3, 80, 64, False), (24, 2000, 8, 80, 256, True),
                                                        (6, 1024, 8, 1500, 256, True)])
-def test_weight_gradient_kernel_plans_vs_oracle(dev, precision, B, Tn, depth, aux, ch, planned):
+def test_weight_gradient_kernel_plans_vs_oracle(dev, precision, request, B, Tn, depth, aux, ch, planned):
     """wgrad16t_kernel (one workgroup per CU, planned phases, wg_wgrad16t.h) at the shipped WN width over several (batch, length, depth,
     conditioning width) combinations: different K ranges, part counts and phase shapes of the two planners -- the two-phase plan of the
     headline shape; the ROUNDS plan for a layer count that does not divide the 8 XCDs and for rows of tiles wider than an XCD (WSRGlow's
     3 659 conditioning channels: 35 column tiles in sub-sets of 7); the headline shape's own K = 24 x 2000 columns; six items of 1024 columns with 1 500 conditioning channels, whose conditioning gradient (12 row
     tiles x 48 column tiles, plane rows that do not divide by the 8 XCDs) walks the XCD-column tile order (ConvGemm16sArgs::xcd_items < 0) -- against the oracle, and a case WITHOUT a plan (a 64-channel WN: its
-    products have 128 rows, the kernel's tiles 256), which must take the two-workgroup kernel and agree as well."""
-    if precision != "bf16x3p":
-        pytest.skip("the grouped weight-gradient launches exist in the S-plane mode only")
+    products have 128 rows, the kernel's tiles 256), which must take the two-workgroup kernel and agree as well.  The grouped launch exists
+    in the S-plane mode only: the other two modes must not take it, and agree with the oracle as well."""
     from constant_memory_waveglow_amd import _lib
     wn = dict(in_channels=4, aux_channels=aux, residual_channels=ch, dilation_channels=ch, skip_channels=ch, depth=depth, radix=3)
     specs = fill.wn_param_specs("F.", 4, aux, ch, ch, ch, depth, 3)
@@ -2173,8 +2183,7 @@ def test_weight_gradient_kernel_plans_vs_oracle(dev, precision, B, Tn, depth, au
     y = fill.normal(tag + "/y", (B, aux, Tn))
     gz = fill.normal(tag + "/gz", x.shape)
     gls = fill.normal(tag + "/gls", (B, 4, Tn))
-    z_ref, _ = orc.coupling_apply(wn, fill.table(specs, P), x, y)
-    ref = orc.coupling_backward(wn, fill.table(specs, P), z_ref, y, gz, gls)
+    z_ref, _, ref = oracle_once(request, lambda: _coupling_oracle(wn, specs, P, x, y, gz, gls))
     blk = cm.AffineCouplingBlock(cm.WN, True, zero_init=False, **wn)
     blk.load_state_dict({n: torch.from_numpy(v) for n, v in P.items()})
     blk = blk.to(dev)
@@ -2183,7 +2192,7 @@ def test_weight_gradient_kernel_plans_vs_oracle(dev, precision, B, Tn, depth, au
     z, ls = blk(xt.clone(), yt)
     ((z * T(gz, dev)).sum() + (ls * T(gls, dev)).sum()).backward()
     torch.cuda.synchronize()
-    assert (_lib.lib().wg_stat_wgrad16t_launches() - before == 1) == planned
+    assert (_lib.lib().wg_stat_wgrad16t_launches() - before == 1) == (planned and precision == SPLANE)
     # (the forward too: six items of 1024 columns with 1 500 conditioning channels is the one shape here whose gate convs are cut along K while
     # the skip path runs in its rank form -- the end conv must then read the gate planes, not partial rows nobody wrote)
     assert np.abs(npy(z) - z_ref).max() < Z_ATOL

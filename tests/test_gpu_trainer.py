@@ -287,3 +287,38 @@ def test_engine_follows_the_tensors_device_not_the_current_one(dev):
     assert torch.equal(z0, z1)
     with pytest.raises(cm.WgError):
         engine.require_device(x, ht.cpu())
+
+
+@pytest.mark.parametrize("model", ["waveglow", "waveflow", "wsrglow"])
+def test_bench_dump_outputs_hold_the_last_step(dev, tmp_path, model):
+    """bench.py --dump-outputs on the timed path itself: make_workload's step records the loss / z / logdet it computed, dump_outputs writes
+    them with the gradients the step left in p.grad (a seeded sample at fixed ascending positions over named_parameters() order).  Checked
+    against the step's own return value, the gradients read back directly, and an independent forward of the model on the same inputs."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_under_test", os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(
+        __file__))), "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    wl = bench.make_workload(model, dev, 2, 0)
+    for _ in range(2):
+        loss = wl["step"]()
+    torch.cuda.synchronize()
+    flat = torch.cat([p.grad.reshape(-1) for _, p in wl["model"].named_parameters() if p.grad is not None]).cpu().numpy()
+    rep = bench.dump_outputs(str(tmp_path), wl)
+    got = {k: np.load(os.path.join(str(tmp_path), k + ".npy")) for k in rep["arrays"]}
+    assert all(a.dtype == np.float32 for a in got.values())
+    assert sum(os.path.getsize(os.path.join(str(tmp_path), f)) for f in os.listdir(str(tmp_path))) <= bench.DUMP_BUDGET_BYTES
+    assert got["loss"].tolist() == [float(np.float32(float(loss)))]
+    k = rep["arrays"]["grads"]["written"]
+    pos = np.sort(np.random.default_rng(bench.DUMP_SEED).choice(flat.size, k, replace=False)) if k < flat.size else slice(None)
+    assert np.array_equal(got["grads"], flat[pos])
+    with torch.no_grad():
+        if model == "wsrglow":
+            z, logdet = wl["model"](wl["x"], wl["h"].clone())
+        else:
+            z, logdet = wl["model"](wl["x"], wl["h"])
+    z, logdet = z.cpu().numpy(), logdet.cpu().numpy()
+    assert got["z"].shape == z.shape and np.abs(got["z"] - z).max() <= 1e-5 * max(1.0, float(np.abs(z).max()))
+    assert np.all(np.abs(got["logdet"] - logdet) <= 1e-4 * np.abs(logdet) + 1e-2)
+    if wl["trainer"] is not None:
+        assert np.array_equal(got["logged"], wl["trainer"].metrics.cpu().numpy())
