@@ -25,6 +25,8 @@ ABI_SYMBOLS = [
     "wg_timer_read_name", "wg_box_probe_bytes", "wg_box_probe", "wg_stat_layerg_launches", "wg_stat_gate_split_launches",
     "wg_wf_wn_backward", "wg_layer_backward_workspace_bytes", "wg_layer_backward", "wg_affine_apply", "wg_affine_backward",
     "wg_reload_env", "wg_stat_gate_part_launches", "wg_wsr_cond_pre",
+    "wg_mg_gemm_workspace_bytes", "wg_mg_gemm", "wg_mg_bn_stats", "wg_mg_bn_update", "wg_mg_bn_tanh", "wg_mg_bn_tanh_backward", "wg_mg_weight_norm",
+    "wg_mg_weight_norm_backward", "wg_lvc_check", "wg_lvc_forward", "wg_lvc_backward_data", "wg_lvc_backward_weight", "wg_lvc_gate_backward",
 ]
 K_CONV_STORE, K_CONV_GATE, K_CONV_RESSKIP, K_CONV_DGATE, K_WGRAD, K_LAYER, K_THIN = range(7)
 
@@ -46,6 +48,16 @@ class WgWnDims(C.Structure):
 
 class WgLayerDims(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("res_ch", "dil_ch", "skip_ch", "radix", "dilation", "last_layer", "h_dilation", "rows")]
+
+
+class WgMgGemmDesc(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("M", "N", "K", "batch", "N1", "K1")] + \
+               [(n, C.c_int64) for n in ("a_m", "a_k", "a_k2", "a_b", "b_k", "b_k2", "b_n", "b_n2", "b_b", "c_m", "c_n", "c_n2", "c_b")] + \
+               [("alpha", C.c_float), ("beta", C.c_float)]
+
+
+class WgLvcDims(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("res_ch", "dil_ch", "radix", "dilation")]
 
 
 PREC_F32, PREC_BF16X3, PREC_BF16X3_PLANES = 0, 1, 2
@@ -168,6 +180,21 @@ def lib():
     L.wg_stat_gate_part_launches.restype = C.c_longlong
     L.wg_reload_env.restype = None
     L.wg_reload_env.argtypes = []
+    L.wg_mg_gemm_workspace_bytes.restype = sz
+    L.wg_mg_gemm_workspace_bytes.argtypes = [C.POINTER(WgMgGemmDesc)]
+    L.wg_mg_gemm.argtypes = [C.POINTER(WgMgGemmDesc), vp, vp, vp, vp, vp, sz, vp]
+    L.wg_mg_bn_stats.argtypes = [vp, i, i, f, i, vp, vp, vp, vp, vp, vp]
+    L.wg_mg_bn_update.argtypes = [vp, vp, vp, vp, vp, i, f, vp]
+    L.wg_mg_bn_tanh.argtypes = [vp, i, i, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.wg_mg_bn_tanh_backward.argtypes = [vp, vp, vp, i, i, vp, vp, vp, i, vp, vp, vp, vp]
+    L.wg_mg_weight_norm.argtypes = [vp, vp, i, i, vp, vp]
+    L.wg_mg_weight_norm_backward.argtypes = [vp, vp, vp, i, i, vp, vp, vp]
+    lvcp = C.POINTER(WgLvcDims)
+    L.wg_lvc_check.argtypes = [lvcp, i, i, i]
+    L.wg_lvc_forward.argtypes = [lvcp, vp, vp, i, i, i, vp, vp, vp]
+    L.wg_lvc_backward_data.argtypes = [lvcp, vp, vp, vp, i, i, i, vp, vp]
+    L.wg_lvc_backward_weight.argtypes = [lvcp, vp, vp, i, i, i, vp, vp]
+    L.wg_lvc_gate_backward.argtypes = [vp, vp, i, i, i, vp, vp]
     _LIB = L
     return L
 

@@ -17,6 +17,7 @@
 #include "wg_layer16q.h"
 #include "wg_thin.h"
 #include "wg_probe.h"
+#include "wg_lvc.h"
 
 #include <algorithm>
 #include <atomic>

@@ -781,3 +781,131 @@ def lowpass(x, n_fft, hop, cut_bins, step):
     out = torch.empty(B, (T + step - 1) // step, dtype=torch.float32, device=x.device)
     check(_lib.lib().wg_lowpass(_p(x), B, T, int(n_fft), int(hop), int(cut_bins), int(step), _p(out), _p(ws), ws.numel(), _stream()), "wg_lowpass")
     return out
+
+
+# ---- MelGlow building blocks (include/wgflow.h wg_mg_* / wg_lvc_*; kernels in csrc/wg_lvc.h) ----------------------------------------
+def mg_gemm(A, B, out, M, N, K, a, b, c, batch=1, N1=None, K1=None, add=None, alpha=1.0, beta=1.0):
+    """out[bt] = alpha A[bt] B[bt] (+ beta add[bt]) with the element strides a = (a_m, a_k, a_k2, a_b), b = (b_k, b_k2, b_n, b_n2, b_b),
+    c = (c_m, c_n, c_n2, c_b) of wg_mg_gemm_desc; the tensors' data pointers are the origins.  A split-K product gets its partial-sum
+    workspace from torch's caching allocator (wg_mg_gemm_workspace_bytes)."""
+    d = _lib.WgMgGemmDesc(M, N, K, batch, N1 or N, K1 or K, *a, *b, *c, alpha, beta)
+    L = _lib.lib()
+    nbytes = L.wg_mg_gemm_workspace_bytes(C.byref(d))
+    ws = torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=out.device) if nbytes else None
+    check(L.wg_mg_gemm(C.byref(d), _p(A), _p(B), _p(add), _p(out), _p(ws), nbytes, _stream(out.device)), "wg_mg_gemm")
+    return out
+
+
+def mg_conv1x1(w, x, out=None, add=None, transpose=False):
+    """1x1 conv batched over items: out[b] = w x[b] (+ add[b]); w [M, K] row-major (transpose: w is [K, M] and w^T is applied).
+    x [B, K, T] contiguous."""
+    Bn, K, T = x.shape
+    M = w.size(1) if transpose else w.size(0)
+    if out is None:
+        out = torch.empty((Bn, M, T), dtype=torch.float32, device=x.device)
+    a = (1, M, 0, 0) if transpose else (K, 1, 0, 0)
+    return mg_gemm(w, x, out, M, T, K, a, (T, 0, 1, 0, K * T), (T, 1, 0, M * T), batch=Bn, add=add)
+
+
+def mg_conv1x1_wgrad(dy, x, out):
+    """out[M, K] = sum over items and positions of dy[b] x[b]^T (dy [B, M, T], x [B, K, T] contiguous; out rows contiguous)."""
+    Bn, M, T = dy.shape
+    K = x.size(1)
+    return mg_gemm(dy, x, out, M, K, T * Bn, (T, 1, M * T, 0), (1, K * T, T, 0, 0), (K, 1, 0, 0), K1=T)
+
+
+def mg_grouped(w, x, G, out=None, add=None, transpose=False):
+    """Grouped 1x1 conv on [channels, N] activations: w [G * Mg, Kg] (transpose: the product with each group's w^T)."""
+    Mg, Kg = w.size(0) // G, w.size(1)
+    Mo, Ko = (Kg, Mg) if transpose else (Mg, Kg)
+    N = x.size(1)
+    if out is None:
+        out = torch.empty((G * Mo, N), dtype=torch.float32, device=x.device)
+    a = (1, Kg, 0, Mg * Kg) if transpose else (Kg, 1, 0, Mg * Kg)
+    return mg_gemm(w, x, out, Mo, N, Ko, a, (N, 0, 1, 0, Ko * N), (N, 1, 0, Mo * N), batch=G, add=add)
+
+
+def mg_grouped_wgrad(dy, x, G, out):
+    """out[G * Mg, Kg] = per group dy_g x_g^T over the N columns (dy [G * Mg, N], x [G * Kg, N])."""
+    N = dy.size(1)
+    Mg, Kg = dy.size(0) // G, x.size(0) // G
+    return mg_gemm(dy, x, out, Mg, Kg, N, (N, 1, 0, Mg * N), (1, 0, N, 0, Kg * N), (Kg, 1, 0, Mg * Kg), batch=G)
+
+
+def mg_bn_stats(x, eps, train, running_mean, running_var):
+    Cn, N = x.shape
+    mean, invstd, var_unb = (torch.empty(Cn, dtype=torch.float32, device=x.device) for _ in range(3))
+    check(_lib.lib().wg_mg_bn_stats(_p(x), Cn, N, float(eps), int(train), _p(running_mean), _p(running_var), _p(mean), _p(invstd),
+                                    _p(var_unb), _stream(x.device)), "wg_mg_bn_stats")
+    return mean, invstd, var_unb
+
+
+def mg_bn_update(running_mean, running_var, num_batches_tracked, mean, var_unb, momentum):
+    check(_lib.lib().wg_mg_bn_update(_p(running_mean), _p(running_var), _p(num_batches_tracked), _p(mean), _p(var_unb), mean.numel(),
+                                     float(momentum), _stream(mean.device)), "wg_mg_bn_update")
+
+
+def mg_bn_tanh(x, mean, invstd, gamma, beta, res=None):
+    Cn, N = x.shape
+    s = torch.empty_like(x)
+    total = torch.empty_like(x) if res is not None else None
+    check(_lib.lib().wg_mg_bn_tanh(_p(x), Cn, N, _p(mean), _p(invstd), _p(gamma), _p(beta), _p(res), _p(s), _p(total),
+                                   _stream(x.device)), "wg_mg_bn_tanh")
+    return s, total
+
+
+def mg_bn_tanh_backward(ds, s, x, mean, invstd, gamma, train, dgamma=None, dbeta=None):
+    Cn, N = x.shape
+    dx = torch.empty_like(x)
+    check(_lib.lib().wg_mg_bn_tanh_backward(_p(ds), _p(s), _p(x), Cn, N, _p(mean), _p(invstd), _p(gamma), int(train), _p(dx), _p(dgamma),
+                                            _p(dbeta), _stream(x.device)), "wg_mg_bn_tanh_backward")
+    return dx
+
+
+def mg_weight_norm(g, v):
+    rows = v.size(0)
+    w = torch.empty((rows, v[0].numel()), dtype=torch.float32, device=v.device)
+    check(_lib.lib().wg_mg_weight_norm(_p(g), _p(v), rows, w.size(1), _p(w), _stream(v.device)), "wg_mg_weight_norm")
+    return w
+
+
+def mg_weight_norm_backward(g, v, dw):
+    dg, dv = torch.empty_like(g), torch.empty_like(v)
+    rows = v.size(0)
+    check(_lib.lib().wg_mg_weight_norm_backward(_p(g), _p(v), _p(dw), rows, v[0].numel(), _p(dg), _p(dv), _stream(v.device)),
+          "wg_mg_weight_norm_backward")
+    return dg, dv
+
+
+def lvc_check(dims, B, T, F):
+    """0, or the library's error code for a shape its LVC kernels do not serve (wg_lvc_check; no launch, no device needed)."""
+    return _lib.lib().wg_lvc_check(C.byref(dims), B, T, F)
+
+
+def lvc_forward(dims, x, w, F):
+    Bn, R, T = x.shape
+    z = torch.empty((Bn, 2 * dims.dil_ch, T), dtype=torch.float32, device=x.device)
+    gate = torch.empty((Bn, dims.dil_ch, T), dtype=torch.float32, device=x.device)
+    check(_lib.lib().wg_lvc_forward(C.byref(dims), _p(x), _p(w), Bn, T, F, _p(z), _p(gate), _stream(x.device)), "wg_lvc_forward")
+    return z, gate
+
+
+def lvc_backward_data(dims, dz, w, F, dx_add=None):
+    Bn, _, T = dz.shape
+    dx = torch.empty((Bn, dims.res_ch, T), dtype=torch.float32, device=dz.device)
+    check(_lib.lib().wg_lvc_backward_data(C.byref(dims), _p(dz), _p(w), _p(dx_add), Bn, T, F, _p(dx), _stream(dz.device)),
+          "wg_lvc_backward_data")
+    return dx
+
+
+def lvc_backward_weight(dims, dz, x, F, out):
+    Bn, _, T = dz.shape
+    check(_lib.lib().wg_lvc_backward_weight(C.byref(dims), _p(dz), _p(x), Bn, T, F, _p(out), _stream(dz.device)), "wg_lvc_backward_weight")
+    return out
+
+
+def lvc_gate_backward(z, dgate):
+    Bn, D, T = dgate.shape
+    dz = torch.empty_like(z)
+    check(_lib.lib().wg_lvc_gate_backward(_p(z), _p(dgate), Bn, D, T, _p(dz), _stream(z.device)), "wg_lvc_gate_backward")
+    return dz

@@ -363,6 +363,69 @@ int wg_affine_apply(const float *in, const float *log_s, const float *t, size_t 
 int wg_affine_backward(const float *out_half, const float *log_s, const float *t, const float *dout, const float *dlog_s, size_t n, int reverse,
                        float *in_rebuilt, float *g_log_s, float *g_t, float *din, void *stream);
 
+/* ---- MelGlow (model/melglow.py upstream): the location-variable-convolution WN and its kernel predictor ---------------------
+ * Appended to revision 9 without changing any earlier declaration.  Building blocks, each one launch (or a few) on the caller's
+ * stream; the composition (Predictor, NonCausalLayerLVC, WN_LVC) is driven from melglow.py.  Exact fp32 (fma chains on the vector
+ * ALUs): the result does not depend on WG_PREC_*.  None of them needs a workspace: every buffer is an argument.  Every reduction
+ * has a fixed order (no atomics), so a recompute reproduces its forward bit for bit. */
+
+/* C[b] = alpha * op(A)[b] op(B)[b] + beta * D[b] (D nullable: then the beta term is absent; D may alias C) with element strides:
+ *   A[m][k] at a_b*b + a_m*m + a_k*(k % K1) + a_k2*(k / K1)
+ *   B[k][n] at b_b*b + b_k*(k % K1) + b_k2*(k / K1) + b_n*(n % N1) + b_n2*(n / N1)
+ *   C[m][n] at c_b*b + c_m*m + c_n*(n % N1) + c_n2*(n / N1)          (D: the same offsets)
+ * The two-level N / K axes read a [B, C, F] tensor as [C, B * F] columns, or sum a weight gradient over items and positions.
+ * A product with few output tiles and a long K (a weight gradient) is cut along K into slices whose partial sums go to the
+ * workspace and are added in slice order (deterministic); ws: wg_mg_gemm_workspace_bytes(d) bytes (0: none needed, ws may be NULL). */
+typedef struct wg_mg_gemm_desc {
+    int32_t M, N, K, batch;
+    int32_t N1, K1;
+    int64_t a_m, a_k, a_k2, a_b;
+    int64_t b_k, b_k2, b_n, b_n2, b_b;
+    int64_t c_m, c_n, c_n2, c_b;
+    float alpha, beta;
+} wg_mg_gemm_desc;
+size_t wg_mg_gemm_workspace_bytes(const wg_mg_gemm_desc *d);
+int wg_mg_gemm(const wg_mg_gemm_desc *d, const float *A, const float *B, const float *D, float *C, void *ws, size_t ws_bytes,
+               void *stream);
+
+/* BatchNorm1d over rows of x[C][N] (N = B * frames).  stats: train = 1 -> batch mean, 1/sqrt(biased var + eps) and the unbiased
+ * variance (sums in double, fixed order); train = 0 -> the same three from running_mean / running_var.
+ * update: running = momentum * batch + (1 - momentum) * running (the unbiased variance for running_var), ++*num_batches_tracked
+ * (nullable) -- a launch of its own, so that the caller decides when the running statistics move.
+ * tanh: s = tanh((x - mean) * invstd * gamma + beta), sum = s + res (res nullable; gamma / beta nullable = affine off).
+ * tanh_backward: from ds (gradient of s): dx with batch statistics (train = 1) or constants (train = 0), dgamma / dbeta (nullable). */
+int wg_mg_bn_stats(const float *x, int C, int N, float eps, int train, const float *running_mean, const float *running_var, float *mean,
+                   float *invstd, float *var_unbiased, void *stream);
+int wg_mg_bn_update(float *running_mean, float *running_var, int64_t *num_batches_tracked, const float *mean, const float *var_unbiased,
+                    int C, float momentum, void *stream);
+int wg_mg_bn_tanh(const float *x, int C, int N, const float *mean, const float *invstd, const float *gamma, const float *beta,
+                  const float *res, float *s, float *sum, void *stream);
+int wg_mg_bn_tanh_backward(const float *ds, const float *s, const float *x, int C, int N, const float *mean, const float *invstd,
+                           const float *gamma, int train, float *dx, float *dgamma, float *dbeta, void *stream);
+
+/* weight norm over dim 0 of a [rows][cols] weight: w = g v / ||v||, and its backward (dg nullable). */
+int wg_mg_weight_norm(const float *g, const float *v, int rows, int cols, float *w, void *stream);
+int wg_mg_weight_norm_backward(const float *g, const float *v, const float *dw, int rows, int cols, float *dg, float *dv, void *stream);
+
+/* NonCausalLayerLVC's dilated conv (model/melglow.py:75-90): x[B][R][T], T = F * L (L columns per frame), per-frame kernels
+ * w[B][F][2D][R][radix] (each frame's block contiguous), padding dilation * (radix - 1) / 2 on both sides of the whole signal:
+ *   z[b][o][fL + t] = sum_{ci,k} w[b][f][o][ci][k] x[b][ci][fL + t + (k - radix/2) dilation]   (zero outside [0, T))
+ *   gate = tanh(z[:, :D]) * sigmoid(z[:, D:])                                                 (fused_gate, waveglow.py:13-15)
+ * backward_data: dx = dx_add (nullable; may alias dx) + the transpose of that map, summed over the overlapping frame windows
+ * by gathering (no atomics).  backward_weight: dw[b][f] = dz over the frame's columns times the unfolded window.
+ * gate_backward: dz[B][2D][T] from z and the gate's gradient dgate[B][D][T].
+ * check: WG_OK, or why the kernels do not serve the shape: even radix (WG_EUNSUPPORTED), T % F (WG_ESHAPE), D > 128, R > 128,
+ * R * radix > 256, L > 128, D * L or R * L > 2048 (WG_EUNSUPPORTED).  The launching entry points run the same check first. */
+typedef struct wg_lvc_dims {
+    int32_t res_ch, dil_ch, radix, dilation;
+} wg_lvc_dims;
+int wg_lvc_check(const wg_lvc_dims *d, int B, int T, int F);
+int wg_lvc_forward(const wg_lvc_dims *d, const float *x, const float *w, int B, int T, int F, float *z, float *gate, void *stream);
+int wg_lvc_backward_data(const wg_lvc_dims *d, const float *dz, const float *w, const float *dx_add, int B, int T, int F, float *dx,
+                         void *stream);
+int wg_lvc_backward_weight(const wg_lvc_dims *d, const float *dz, const float *x, int B, int T, int F, float *dw, void *stream);
+int wg_lvc_gate_backward(const float *z, const float *dgate, int B, int D, int T, float *dz, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
