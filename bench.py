@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Headline benchmark: audio samples/s of WaveGlow-256ch forward + NLL backward on 16 000-sample segments.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--no-cpu] [--no-inverse] [--spawn] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--spawn] [--dump-outputs DIR]
+                    [--full [--no-cpu] [--no-inverse] [--no-extra] [--no-box]]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -16,7 +17,11 @@ z, logdet = model(x, h); loss = NLL(z, logdet); backward to all 459 parameter gr
 of the gradients when N > 1).  Data loading, mel computation, optimizer step and logging are outside, as in
 SURVEY.md 8d.  Per-GPU batch is fixed (weak scaling): configs[1] of BASELINE.json at N=1, configs[2] at N=8.
 
-Rank 0 prints ONE JSON line with the contract fields plus
+Rank 0 prints ONE JSON line with the contract fields (metric, value, unit, higher_is_better, dtype, ms_per_step, ...), the loss and
+logged scalars of the last timed step, and `dump_outputs` when --dump-outputs is given.  That is all a plain run does after its warm-up
+and timed steps.  `--full` measures the rest behind the timed steps and adds
+  comm         : (N > 1) bytes and buckets of the gradient exchange, every rank's step time, and the same step with the collectives
+                 skipped (`exposed_ms`);
   roofline     : the dominant kernel (dilated conv + conditioning + gate; the line names the instantiation that RAN, as the library
                  reports it per launch: wg_timer_read_name) timed with HIP events over as many EXTRA steps behind the timed ones
                  (nothing is attached while the headline runs), algorithmic FLOPs / average launch duration vs the dense bf16 MFMA peak
@@ -26,8 +31,10 @@ Rank 0 prints ONE JSON line with the contract fields plus
                  on) timed on the host cores on one 16 000-sample segment of the same workload (rank 0, N=1 only), with the plain-C
                  oracle next to it as `c_port`;
   inverse_khz  : single-GPU synthesis speed, timed as the reference does (inference.py:50-56);
-  box          : a fixed matrix-pipe + LDS loop of the library (wg_box_probe, ~0.5 s before the warm-up is over): issued TFLOP/s and the
-                 in-kernel clock of THIS GPU -- the boxes of the pool differ by a few per cent, this makes that a measured field.
+  box          : a fixed matrix-pipe + LDS loop of the library (wg_box_probe, ~0.5 s behind the timed steps): issued TFLOP/s and the
+                 in-kernel clock of THIS GPU -- the boxes of the pool differ by a few per cent, this makes that a measured field;
+  and on one GPU per-shape rooflines (`roofline.kernels`), for WaveGlow also `adam_step_ms`, `f32_mode` and `other_models`.  The
+--no-* flags leave parts of a --full run out.
 """
 import argparse
 import ctypes as C
@@ -49,7 +56,7 @@ SEG, FRAMES, SIGMA = 16000, 63, 0.7
 # the config behind the ONLY speed the reference publishes ("around 470 kHz on a 1080ti", README.md:64-67): configs/musicnet_config.json:7-20
 MUSICNET = dict(flows=18, n_group=8, n_early_every=6, n_early_size=2, hop_size=512, n_mels=80,
                 dilation_channels=256, residual_channels=256, skip_channels=256, depth=4, radix=3)
-MUSICNET_PUBLISHED_KHZ = 470.0            # /root/reference/README.md:67 (GTX 1080 Ti)
+MUSICNET_PUBLISHED_KHZ = 470.0            # the reference's README.md:67 (GTX 1080 Ti)
 FP32_MFMA_PEAK_TFLOPS = 157.3            # MI355X_MICROARCH.md, "Peak FP32 (matrix)"
 BF16_MFMA_PEAK_TFLOPS = 2500.0           # MI355X_MICROARCH.md, "Peak BF16/FP16 MFMA" (dense)
 FWD_FLOP_PER_SAMPLE = 13_376_372         # SURVEY.md 2.1 (forward = inverse)
@@ -685,10 +692,13 @@ def parse_args(argv=None):
                     help="waveglow: BASELINE.json configs[1] / [2] (the headline); waveflow: configs[3] (waveflow_LJ_speech.json); "
                          "wsrglow: configs[4] (wsrglow_vctk_2x.json) -- same launcher, same JSON contract")
     ap.add_argument("--batch", type=int, default=None, help="per-GPU batch (default: the model's config -- 24 / 12 / 12)")
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-inverse", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the WSRGlow / WaveFlow step timings (SURVEY.md 8f rows)")
-    ap.add_argument("--no-box", action="store_true", help="skip the 0.5 s box-calibration probe (`box` in the line)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, measure everything else the line can carry (roofline, box, comm, synthesis, Adam, per-shape "
+                         "rooflines, f32_mode, other_models, cpu_baseline); without it the run does only the headline")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU baseline (`cpu_baseline`)")
+    ap.add_argument("--no-inverse", action="store_true", help="with --full: skip the synthesis timings (`inverse_*`)")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the exact-fp32 mode and the WSRGlow / WaveFlow step timings (SURVEY.md 8f rows)")
+    ap.add_argument("--no-box", action="store_true", help="with --full: skip the 0.5 s box-calibration probe (`box` in the line)")
     ap.add_argument("--spawn", action="store_true", help="go through the launcher even for --gpus 1 (a 1-rank RCCL group)")
     ap.add_argument("--dry-run", action="store_true", help="launcher only: print the child command and environment as JSON, start nothing")
     ap.add_argument("--oversubscribe", action="store_true",
@@ -781,6 +791,203 @@ def selftest_rank(args, world, rank):
     return 0
 
 
+def full_report(out, args, wl, dev, use_dist, world, rank, dt_own, ms_per_step, barrier):
+    """--full: what the line carries beyond its headline, all of it measured behind the timed steps -- the gradient exchange (N > 1),
+    the box probe, the dominant kernel's roofline over as many extra steps as were timed and, on rank 0, synthesis, the Adam step,
+    per-shape rooflines, the exact-fp32 mode, the other models and the CPU baseline, as the --no-* flags leave them.  Every rank runs
+    the extra steps (the collectives need all ranks); rank 0 adds its fields to its line `out`."""
+    from constant_memory_waveglow_amd import _lib
+    L = _lib.lib()
+    model, trainer, x, h, g, step = wl["model"], wl["trainer"], wl["x"], wl["h"], wl["generator"], wl["step"]
+    comm = comm_report(wl, args, use_dist, world, rank, dev, dt_own, ms_per_step, barrier) if use_dist else None
+    # (behind the timed steps: half a second of full-power matrix work on ONE rank in front of a max-reduced multi-rank headline would
+    # heat that rank's GPU alone; the other ranks wait at the barrier below)
+    box = box_probe(dev) if rank == 0 and not args.no_box else None
+    # the dominant kernel's launch duration: HIP events around every launch of its class over `args.steps` EXTRA steps (every rank runs
+    # them: the collectives need all ranks), outside the timed region; the library reports which instantiation each launch ran
+    # (every class is timed: the gate conv runs on its own -- class K_CONV_GATE -- or, at the training shapes since round 5, inside the
+    # one-launch layer -- K_LAYER: gate conv + residual product; the roofline describes whichever takes more of the step)
+    timer = L.wg_timer_create(-1, 4096 * args.steps) if rank == 0 else None
+    barrier()
+    if timer:
+        L.wg_timer_attach(timer)
+    for _ in range(args.steps):
+        step()
+    barrier()
+    if timer:
+        L.wg_timer_attach(None)
+    if rank != 0:
+        return
+    n_all = L.wg_timer_count(timer)
+    buf = (C.c_float * n_all)()
+    info = (C.c_longlong * (5 * n_all))()
+    L.wg_timer_read(timer, buf, n_all)
+    L.wg_timer_read_info(timer, info, n_all)
+    ms_all = np.frombuffer(buf, dtype=np.float32)
+    info = np.frombuffer(info, dtype=np.int64).reshape(n_all, 5)
+    per_class = {c: float(ms_all[info[:, 0] == c].sum()) for c in (_lib.K_CONV_GATE, _lib.K_LAYER)}
+    dom = max(per_class, key=per_class.get)
+    sel = np.nonzero(info[:, 0] == dom)[0]
+    # (a class holds launches of more than one K since the first layer's conv reads xa through the composed weight -- DESIGN.md 4g: its
+    # gate conv is a few chunks long.  The roofline line is about the full-K launches: the others would be credited FLOPs they do not do)
+    if sel.size:
+        sel = sel[info[sel, 2] == info[sel, 2].max()]
+    names = {}
+    nb = C.create_string_buffer(256)
+    for i in sel:
+        if L.wg_timer_read_name(timer, int(i), nb, 256) >= 0:
+            names[nb.value.decode()] = names.get(nb.value.decode(), 0) + 1
+    L.wg_timer_destroy(timer)
+    n = int(sel.size)
+    gate_ms = float(np.mean(ms_all[sel])) if n else float("nan")
+    # algorithmic FLOPs of one launch: the gate conv's, or (layer launch) gate conv + residual product: 2 M K columns of what the
+    # library attaches to the launch (wg_timer_read_info: for the layer K counts the residual's channels scaled to the gate's rows)
+    gate_flop = wl["gate_flop_per_launch"] if dom == _lib.K_CONV_GATE or not n else float(2.0 * np.median(info[sel, 1] * info[sel, 2] * info[sel, 3]))
+    what = wl["gate_what"] if dom == _lib.K_CONV_GATE else wl["gate_what"] + ", then W_o's residual rows on the same workgroup (one launch per layer)"
+    achieved = gate_flop / (gate_ms * 1e-3) / 1e12
+    split = _lib.default_precision() != _lib.PREC_F32
+    # bf16x3: every fp32 product costs three bf16 MFMAs; the roofline is the bf16 matrix pipe and only the
+    # algorithmic FLOPs are credited (the 3x is overhead, not work) -- SURVEY.md 8d
+    peak = BF16_MFMA_PEAK_TFLOPS if split else FP32_MFMA_PEAK_TFLOPS
+    # the instantiation most of the timed launches ran (a model may take more than one: small flows, other tile forms)
+    site = max(names, key=names.get) if names else ""
+    kprefix = " + ".join(launch_site_to_rocprof(p) for p in site.split(" + ")) if site else ""
+    traffic, traffic_src, kfull = site_traffic(site, wl["profile_prefix"]) if site else (None, None, None)
+    if traffic_src:
+        traffic_src += " (committed rocprofv3 --pmc summary of this command; not re-measured in this run)"
+    gate_alone = None
+    galone = np.nonzero(info[:, 0] == _lib.K_CONV_GATE)[0]
+    if galone.size:
+        galone = galone[info[galone, 2] == info[galone, 2].max()]
+    if dom == _lib.K_LAYER and galone.size:                          # the gate conv launches that run on their own (a WN's last layer)
+        g_ms = float(np.mean(ms_all[galone]))
+        g_ach = wl["gate_flop_per_launch"] / (g_ms * 1e-3) / 1e12
+        gate_alone = {"launch_ms": g_ms, "launches_timed": int(galone.size), "flop_per_launch": wl["gate_flop_per_launch"], "achieved": g_ach,
+                      "frac": g_ach / peak}
+    out["roofline"] = {"bound": "mfma", "kernel": "%s (EPI_GATE: %s)" % (kfull or " + ".join(p + ">" if "<" in p else p for p in kprefix.split(" + ")), what),
+                       "kernel_launch_sites": names,
+                       "class_ms_timed": {"gate conv on its own": per_class[_lib.K_CONV_GATE], "layer launch": per_class[_lib.K_LAYER]},
+                       **({"gate_conv_alone": gate_alone} if gate_alone else {}),
+                       "achieved": achieved, "peak": peak, "unit": "TFLOP/s", "frac": achieved / peak,
+                       "traffic": traffic, "traffic_source": traffic_src,
+                       "launch_ms": gate_ms, "launches_timed": n, "launch_timing": "HIP events around every launch of the class over %d extra steps "
+                                                                                  "behind the timed ones (nothing is attached while the headline runs)" % args.steps,
+                       "flop_per_launch": gate_flop,
+                       "mfma_tflops_issued": achieved * (3 if split else 1),
+                       # issued TFLOP/s of the dominant launch over what THIS GPU sustains on the library's fixed matrix-pipe + LDS loop
+                       # without global traffic (`box`): separates a slow box from a slow kernel in one number
+                       **({"frac_of_box": achieved * (3 if split else 1) / box["tflops_issued"]} if (box and box.get("tflops_issued") and split) else {}),
+                       "x_fp32_mfma_peak": achieved / FP32_MFMA_PEAK_TFLOPS}
+    if box is not None:
+        out["box"] = box
+    if comm is not None:
+        out["comm"] = comm
+    if args.model != "waveglow":
+        wl["no_inverse"] = args.no_inverse
+        args.no_inverse = args.no_extra = args.no_cpu = True         # the secondary legs belong to the headline workload
+        if world == 1:
+            try:
+                out["roofline"]["kernels"] = kernel_rooflines(trainer, x, h, split, step_fn=step if trainer is None else None,
+                                                                  box_tflops=(box or {}).get("tflops_issued"))
+            except Exception as e:                                    # noqa: BLE001
+                out["roofline"]["kernels"] = {"error": repr(e)}
+        if args.model == "waveflow" and world == 1 and not wl.get("no_inverse"):
+            with torch.no_grad():                                     # synthesis (row-by-row inverse), as inference.py:50-56
+                for frames in (63, 862):
+                    hc = torch.randn(1, 80, frames, device=dev)
+                    model.infer(hc, 0.6)
+                    torch.cuda.synchronize()
+                    t1 = time.perf_counter()
+                    xs = model.infer(hc, 0.6)
+                    torch.cuda.synchronize()
+                    out["inverse_khz_%d" % xs.numel()] = xs.numel() / (time.perf_counter() - t1) / 1000.0
+    if not args.no_inverse:
+        with torch.no_grad():
+            for frames in (63, 862):                                  # 16 128 samples and ~10 s of audio (SURVEY.md 8d)
+                hc = torch.randn(1, C2["n_mels"], frames, device=dev, generator=g)
+                model.infer(hc, 0.6)
+                costs = []
+                for _ in range(5):                                    # one call between two synchronisations, as inference.py:50-56
+                    torch.cuda.synchronize()
+                    t1 = time.perf_counter()
+                    xs = model.infer(hc, 0.6)
+                    torch.cuda.synchronize()
+                    costs.append(time.perf_counter() - t1)
+                out["inverse_khz_%d" % xs.numel()] = xs.numel() / sorted(costs)[2] / 1000.0
+                t1 = time.perf_counter()
+                for _ in range(10):                                   # a queue of utterances: the host runs ahead of the device
+                    xs = model.infer(hc, 0.6)
+                torch.cuda.synchronize()
+                out["inverse_khz_%d_queued" % xs.numel()] = xs.numel() * 10 / (time.perf_counter() - t1) / 1000.0
+        out["inverse_khz"] = out["inverse_khz_%d" % (862 * 256)]
+        # throughput next to latency: the reference's infer takes h[B, ...] (base.py:42-55) -- eight 0.7 s utterances in one call
+        hb = torch.randn(8, C2["n_mels"], 63, device=dev, generator=g)
+        with torch.no_grad():
+            model.infer(hb, 0.6)
+            costs = []
+            for _ in range(5):
+                torch.cuda.synchronize()
+                t1 = time.perf_counter()
+                xs = model.infer(hb, 0.6)
+                torch.cuda.synchronize()
+                costs.append(time.perf_counter() - t1)
+        out["inverse_khz_batch8x16128"] = xs.numel() / sorted(costs)[2] / 1000.0
+        # the reference's published configuration (musicnet: 18 flows, early outputs every 6, WN depth 4, hop 512): 10 s of audio
+        mus = build_model(dev, cfg=MUSICNET)
+        hm = torch.randn(1, MUSICNET["n_mels"], 431, device=dev, generator=g)
+        with torch.no_grad():
+            mus.infer(hm, 0.6)
+            costs = []
+            for _ in range(5):
+                torch.cuda.synchronize()
+                t1 = time.perf_counter()
+                xm = mus.infer(hm, 0.6)
+                torch.cuda.synchronize()
+                costs.append(time.perf_counter() - t1)
+        mus_khz = xm.numel() / sorted(costs)[2] / 1000.0
+        out["inverse_khz_musicnet_%d" % xm.numel()] = mus_khz
+        del mus
+        # synthesis is the forward's FLOPs (13.38 MFLOP per sample) on the same matrix pipe: 2.5 PF bf16, three issued per product
+        peak = BF16_MFMA_PEAK_TFLOPS if split else FP32_MFMA_PEAK_TFLOPS
+        out["inverse_roofline"] = {
+            "bound": "mfma", "unit": "TFLOP/s", "peak": peak, "flop_per_sample": FWD_FLOP_PER_SAMPLE,
+            "cases": {**{str(nn): {"khz": out["inverse_khz_%d" % nn], "achieved": out["inverse_khz_%d" % nn] * 1e3 * FWD_FLOP_PER_SAMPLE / 1e12,
+                                   "frac": out["inverse_khz_%d" % nn] * 1e3 * FWD_FLOP_PER_SAMPLE / 1e12 / peak} for nn in (63 * 256, 862 * 256)},
+                      "8x16128": {"khz": out["inverse_khz_batch8x16128"], "achieved": out["inverse_khz_batch8x16128"] * 1e3 * FWD_FLOP_PER_SAMPLE / 1e12,
+                                  "frac": out["inverse_khz_batch8x16128"] * 1e3 * FWD_FLOP_PER_SAMPLE / 1e12 / peak}},
+            "musicnet": {"config": "configs/musicnet_config.json: 18 flows, n_early_every 6, WN depth 4, hop 512, 80 mels; %d samples" % xm.numel(),
+                         "khz": mus_khz, "flop_per_sample": fwd_flop_per_sample(MUSICNET),
+                         "achieved": mus_khz * 1e3 * fwd_flop_per_sample(MUSICNET) / 1e12,
+                         "frac": mus_khz * 1e3 * fwd_flop_per_sample(MUSICNET) / 1e12 / peak,
+                         "reference_published_khz": MUSICNET_PUBLISHED_KHZ,
+                         "reference_published_on": "GTX 1080 Ti (README.md:64-67 of the reference: 'around 470kHz'); other hardware, quoted for scale",
+                         "x_reference_published": mus_khz / MUSICNET_PUBLISHED_KHZ},
+            "note": "one call between two synchronisations as inference.py:50-56; a 16 128-sample utterance is a chain of ~250 small "
+                    "launches (64 x 64 tiles on every CU, DESIGN.md section 4a iii), the 10 s utterance fills the chip"}
+    if world == 1 and args.model == "waveglow":
+        # outside the metric (SURVEY.md 8d excludes the optimizer): one Adam step over all 53.66 M parameters on the flat buffers
+        from constant_memory_waveglow_amd.parallel import FlatAdam
+        opt = FlatAdam(trainer, lr=1e-4)
+        trainer.optimizer = None                          # timed stand-alone; trainer.step would run it per bucket
+        opt.step()
+        torch.cuda.synchronize()
+        t1 = time.perf_counter()
+        for _ in range(5):
+            opt.step()
+        torch.cuda.synchronize()
+        out["adam_step_ms"] = (time.perf_counter() - t1) / 5 * 1e3
+    if world == 1 and args.model == "waveglow":                   # (extra steps on one rank only would wait for collectives forever)
+        try:
+            out["roofline"]["kernels"] = kernel_rooflines(trainer, x, h, split, box_tflops=(box or {}).get("tflops_issued"))
+        except Exception as e:                                    # noqa: BLE001 -- diagnostics never touch the headline line
+            out["roofline"]["kernels"] = {"error": repr(e)}
+    if world == 1 and not args.no_extra:
+        out["f32_mode"] = f32_mode(dev, x, h)
+        out["other_models"] = other_models(dev)
+    if world == 1 and not args.no_cpu:
+        out["cpu_baseline"] = cpu_baseline()
+
+
 def main(argv=None):
     argv = list(sys.argv[1:] if argv is None else argv)
     args = parse_args(argv)
@@ -823,10 +1030,7 @@ def main(argv=None):
               % (args.gpus, args.gpus, dist.get_backend() if use_dist else None, dist.get_world_size() if use_dist else 0), file=sys.stderr)
         return 2
     wl = make_workload(args.model, dev, args.batch, rank)
-    model, trainer, B, SEGW = wl["model"], wl["trainer"], wl["batch"], wl["segment"]
-    x, h = wl["x"], wl["h"]
-    g = wl["generator"]
-    step = wl["step"]
+    trainer, B, SEGW, step = wl["trainer"], wl["batch"], wl["segment"], wl["step"]
 
     def barrier():
         if use_dist:
@@ -835,8 +1039,6 @@ def main(argv=None):
 
     for _ in range(args.warmup):
         step()
-    L = _lib.lib()
-    per_step_gate = wl["gate_launches_per_step"]
     barrier()
     t0 = time.perf_counter()
     for _ in range(args.steps):                                   # the headline: NOTHING attached, no event beyond the two brackets
@@ -853,72 +1055,9 @@ def main(argv=None):
     dt = float(tmax.item())
     ms_per_step = dt / args.steps * 1e3
     value = world * B * SEGW * args.steps / dt
-    comm = comm_report(wl, args, use_dist, world, rank, dev, dt_own, ms_per_step, barrier) if use_dist else None
-    # (behind the timed steps: half a second of full-power matrix work on ONE rank in front of a max-reduced multi-rank headline would
-    # heat that rank's GPU alone; the other ranks wait at the barrier below)
-    box = box_probe(dev) if rank == 0 and not args.no_box else None
-    # the dominant kernel's launch duration: HIP events around every launch of its class over `args.steps` EXTRA steps (every rank runs
-    # them: the collectives need all ranks), outside the timed region; the library reports which instantiation each launch ran
-    # (every class is timed: the gate conv runs on its own -- class K_CONV_GATE -- or, at the training shapes since round 5, inside the
-    # one-launch layer -- K_LAYER: gate conv + residual product; the roofline describes whichever takes more of the step)
-    timer = L.wg_timer_create(-1, 4096 * args.steps) if rank == 0 else None
-    barrier()
-    if timer:
-        L.wg_timer_attach(timer)
-    for _ in range(args.steps):
-        step()
-    barrier()
-    if timer:
-        L.wg_timer_attach(None)
-
     out = None
     if rank == 0:
-        n_all = L.wg_timer_count(timer)
-        buf = (C.c_float * n_all)()
-        info = (C.c_longlong * (5 * n_all))()
-        L.wg_timer_read(timer, buf, n_all)
-        L.wg_timer_read_info(timer, info, n_all)
-        ms_all = np.frombuffer(buf, dtype=np.float32)
-        info = np.frombuffer(info, dtype=np.int64).reshape(n_all, 5)
-        per_class = {c: float(ms_all[info[:, 0] == c].sum()) for c in (_lib.K_CONV_GATE, _lib.K_LAYER)}
-        dom = max(per_class, key=per_class.get)
-        sel = np.nonzero(info[:, 0] == dom)[0]
-        # (a class holds launches of more than one K since the first layer's conv reads xa through the composed weight -- DESIGN.md 4g: its
-        # gate conv is a few chunks long.  The roofline line is about the full-K launches: the others would be credited FLOPs they do not do)
-        if sel.size:
-            sel = sel[info[sel, 2] == info[sel, 2].max()]
-        names = {}
-        nb = C.create_string_buffer(256)
-        for i in sel:
-            if L.wg_timer_read_name(timer, int(i), nb, 256) >= 0:
-                names[nb.value.decode()] = names.get(nb.value.decode(), 0) + 1
-        L.wg_timer_destroy(timer)
-        n = int(sel.size)
-        gate_ms = float(np.mean(ms_all[sel])) if n else float("nan")
-        # algorithmic FLOPs of one launch: the gate conv's, or (layer launch) gate conv + residual product: 2 M K columns of what the
-        # library attaches to the launch (wg_timer_read_info: for the layer K counts the residual's channels scaled to the gate's rows)
-        gate_flop = wl["gate_flop_per_launch"] if dom == _lib.K_CONV_GATE or not n else float(2.0 * np.median(info[sel, 1] * info[sel, 2] * info[sel, 3]))
-        what = wl["gate_what"] if dom == _lib.K_CONV_GATE else wl["gate_what"] + ", then W_o's residual rows on the same workgroup (one launch per layer)"
-        achieved = gate_flop / (gate_ms * 1e-3) / 1e12
         split = _lib.default_precision() != _lib.PREC_F32
-        # bf16x3: every fp32 product costs three bf16 MFMAs; the roofline is the bf16 matrix pipe and only the
-        # algorithmic FLOPs are credited (the 3x is overhead, not work) -- SURVEY.md 8d
-        peak = BF16_MFMA_PEAK_TFLOPS if split else FP32_MFMA_PEAK_TFLOPS
-        # the instantiation most of the timed launches ran (a model may take more than one: small flows, other tile forms)
-        site = max(names, key=names.get) if names else ""
-        kprefix = " + ".join(launch_site_to_rocprof(p) for p in site.split(" + ")) if site else ""
-        traffic, traffic_src, kfull = site_traffic(site, wl["profile_prefix"]) if site else (None, None, None)
-        if traffic_src:
-            traffic_src += " (committed rocprofv3 --pmc summary of this command; not re-measured in this run)"
-        gate_alone = None
-        galone = np.nonzero(info[:, 0] == _lib.K_CONV_GATE)[0]
-        if galone.size:
-            galone = galone[info[galone, 2] == info[galone, 2].max()]
-        if dom == _lib.K_LAYER and galone.size:                          # the gate conv launches that run on their own (a WN's last layer)
-            g_ms = float(np.mean(ms_all[galone]))
-            g_ach = wl["gate_flop_per_launch"] / (g_ms * 1e-3) / 1e12
-            gate_alone = {"launch_ms": g_ms, "launches_timed": int(galone.size), "flop_per_launch": wl["gate_flop_per_launch"], "achieved": g_ach,
-                          "frac": g_ach / peak}
         STEP_FLOP = wl["step_flop_per_sample"]
         out = {
             "metric": wl["metric"],
@@ -931,138 +1070,18 @@ def main(argv=None):
             "dtype": "f32 (contractions as split bf16x3 MFMA, fp32 accumulate)" if split else "f32", "data": "synthetic",
             "config": {"workload": wl["workload"] + (" + RCCL grad all-reduce" if world > 1 else ""),
                        "global_batch": B * world, "segment": SEGW, "parallelism": "dp%d" % world},
-            "roofline": {"bound": "mfma", "kernel": "%s (EPI_GATE: %s)" % (kfull or " + ".join(p + ">" if "<" in p else p for p in kprefix.split(" + ")), what),
-                         "kernel_launch_sites": names,
-                         "class_ms_timed": {"gate conv on its own": per_class[_lib.K_CONV_GATE], "layer launch": per_class[_lib.K_LAYER]},
-                         **({"gate_conv_alone": gate_alone} if gate_alone else {}),
-                         "achieved": achieved, "peak": peak, "unit": "TFLOP/s", "frac": achieved / peak,
-                         "traffic": traffic, "traffic_source": traffic_src,
-                         "launch_ms": gate_ms, "launches_timed": n, "launch_timing": "HIP events around every launch of the class over %d extra steps "
-                                                                                    "behind the timed ones (nothing is attached while the headline runs)" % args.steps,
-                         "flop_per_launch": gate_flop,
-                         "mfma_tflops_issued": achieved * (3 if split else 1),
-                         # issued TFLOP/s of the dominant launch over what THIS GPU sustains on the library's fixed matrix-pipe + LDS loop
-                         # without global traffic (`box`): separates a slow box from a slow kernel in one number
-                         **({"frac_of_box": achieved * (3 if split else 1) / box["tflops_issued"]} if (box and box.get("tflops_issued") and split) else {}),
-                         "x_fp32_mfma_peak": achieved / FP32_MFMA_PEAK_TFLOPS},
             "step_flop_per_sample": STEP_FLOP,
             "step_tflops_algorithmic": value * STEP_FLOP / 1e12 / world,
             "step_frac_of_fp32_mfma_peak": value * STEP_FLOP / 1e12 / world / FP32_MFMA_PEAK_TFLOPS,
             "step_frac_of_bf16_mfma_peak": value * STEP_FLOP / 1e12 / world / BF16_MFMA_PEAK_TFLOPS,
             "loss": float(loss),
         }
-        if box is not None:
-            out["box"] = box
         if logged is not None:
             out["logged"] = logged                     # the scalars LightModel.training_step logs (lightning.py:58-64), rank-mean, of the last timed step
-        if comm is not None:
-            out["comm"] = comm
         if dumped is not None:
             out["dump_outputs"] = dumped
-        if args.model != "waveglow":
-            wl["no_inverse"] = args.no_inverse
-            args.no_inverse = args.no_extra = args.no_cpu = True         # the secondary legs belong to the headline workload
-            if world == 1:
-                try:
-                    out["roofline"]["kernels"] = kernel_rooflines(trainer, x, h, split, step_fn=step if trainer is None else None,
-                                                                      box_tflops=(box or {}).get("tflops_issued"))
-                except Exception as e:                                    # noqa: BLE001
-                    out["roofline"]["kernels"] = {"error": repr(e)}
-            if args.model == "waveflow" and world == 1 and not wl.get("no_inverse"):
-                with torch.no_grad():                                     # synthesis (row-by-row inverse), as inference.py:50-56
-                    for frames in (63, 862):
-                        hc = torch.randn(1, 80, frames, device=dev)
-                        model.infer(hc, 0.6)
-                        torch.cuda.synchronize()
-                        t1 = time.perf_counter()
-                        xs = model.infer(hc, 0.6)
-                        torch.cuda.synchronize()
-                        out["inverse_khz_%d" % xs.numel()] = xs.numel() / (time.perf_counter() - t1) / 1000.0
-        if not args.no_inverse:
-            with torch.no_grad():
-                for frames in (63, 862):                                  # 16 128 samples and ~10 s of audio
-                    hc = torch.randn(1, C2["n_mels"], frames, device=dev, generator=g)
-                    model.infer(hc, 0.6)
-                    costs = []
-                    for _ in range(5):                                    # one call between two synchronisations, as inference.py:50-56
-                        torch.cuda.synchronize()
-                        t1 = time.perf_counter()
-                        xs = model.infer(hc, 0.6)
-                        torch.cuda.synchronize()
-                        costs.append(time.perf_counter() - t1)
-                    out["inverse_khz_%d" % xs.numel()] = xs.numel() / sorted(costs)[2] / 1000.0
-                    t1 = time.perf_counter()
-                    for _ in range(10):                                   # a queue of utterances: the host runs ahead of the device
-                        xs = model.infer(hc, 0.6)
-                    torch.cuda.synchronize()
-                    out["inverse_khz_%d_queued" % xs.numel()] = xs.numel() * 10 / (time.perf_counter() - t1) / 1000.0
-            out["inverse_khz"] = out["inverse_khz_%d" % (862 * 256)]
-            # throughput next to latency: the reference's infer takes h[B, ...] (base.py:42-55) -- eight 0.7 s utterances in one call
-            hb = torch.randn(8, C2["n_mels"], 63, device=dev, generator=g)
-            with torch.no_grad():
-                model.infer(hb, 0.6)
-                costs = []
-                for _ in range(5):
-                    torch.cuda.synchronize()
-                    t1 = time.perf_counter()
-                    xs = model.infer(hb, 0.6)
-                    torch.cuda.synchronize()
-                    costs.append(time.perf_counter() - t1)
-            out["inverse_khz_batch8x16128"] = xs.numel() / sorted(costs)[2] / 1000.0
-            # the reference's published configuration (musicnet: 18 flows, early outputs every 6, WN depth 4, hop 512): 10 s of audio
-            mus = build_model(dev, cfg=MUSICNET)
-            hm = torch.randn(1, MUSICNET["n_mels"], 431, device=dev, generator=g)
-            with torch.no_grad():
-                mus.infer(hm, 0.6)
-                costs = []
-                for _ in range(5):
-                    torch.cuda.synchronize()
-                    t1 = time.perf_counter()
-                    xm = mus.infer(hm, 0.6)
-                    torch.cuda.synchronize()
-                    costs.append(time.perf_counter() - t1)
-            mus_khz = xm.numel() / sorted(costs)[2] / 1000.0
-            out["inverse_khz_musicnet_%d" % xm.numel()] = mus_khz
-            del mus
-            # synthesis is the forward's FLOPs (13.38 MFLOP per sample) on the same matrix pipe: 2.5 PF bf16, three issued per product
-            peak = BF16_MFMA_PEAK_TFLOPS if split else FP32_MFMA_PEAK_TFLOPS
-            out["inverse_roofline"] = {
-                "bound": "mfma", "unit": "TFLOP/s", "peak": peak, "flop_per_sample": FWD_FLOP_PER_SAMPLE,
-                "cases": {**{str(nn): {"khz": out["inverse_khz_%d" % nn], "achieved": out["inverse_khz_%d" % nn] * 1e3 * FWD_FLOP_PER_SAMPLE / 1e12,
-                                       "frac": out["inverse_khz_%d" % nn] * 1e3 * FWD_FLOP_PER_SAMPLE / 1e12 / peak} for nn in (63 * 256, 862 * 256)},
-                          "8x16128": {"khz": out["inverse_khz_batch8x16128"], "achieved": out["inverse_khz_batch8x16128"] * 1e3 * FWD_FLOP_PER_SAMPLE / 1e12,
-                                      "frac": out["inverse_khz_batch8x16128"] * 1e3 * FWD_FLOP_PER_SAMPLE / 1e12 / peak}},
-                "musicnet": {"config": "configs/musicnet_config.json: 18 flows, n_early_every 6, WN depth 4, hop 512, 80 mels; %d samples" % xm.numel(),
-                             "khz": mus_khz, "flop_per_sample": fwd_flop_per_sample(MUSICNET),
-                             "achieved": mus_khz * 1e3 * fwd_flop_per_sample(MUSICNET) / 1e12,
-                             "frac": mus_khz * 1e3 * fwd_flop_per_sample(MUSICNET) / 1e12 / peak,
-                             "reference_published_khz": MUSICNET_PUBLISHED_KHZ,
-                             "reference_published_on": "GTX 1080 Ti (README.md:64-67 of the reference: 'around 470kHz'); other hardware, quoted for scale",
-                             "x_reference_published": mus_khz / MUSICNET_PUBLISHED_KHZ},
-                "note": "one call between two synchronisations as inference.py:50-56; a 16 128-sample utterance is a chain of ~250 small "
-                        "launches (64 x 64 tiles on every CU, DESIGN.md section 4a iii), the 10 s utterance fills the chip"}
-        if world == 1 and args.model == "waveglow":
-            # outside the metric (SURVEY.md 8d excludes the optimizer): one Adam step over all 53.66 M parameters on the flat buffers
-            from constant_memory_waveglow_amd.parallel import FlatAdam
-            opt = FlatAdam(trainer, lr=1e-4)
-            trainer.optimizer = None                          # timed stand-alone; trainer.step would run it per bucket
-            opt.step()
-            torch.cuda.synchronize()
-            t1 = time.perf_counter()
-            for _ in range(5):
-                opt.step()
-            torch.cuda.synchronize()
-            out["adam_step_ms"] = (time.perf_counter() - t1) / 5 * 1e3
-        if world == 1 and args.model == "waveglow":                   # (extra steps on one rank only would wait for collectives forever)
-            try:
-                out["roofline"]["kernels"] = kernel_rooflines(trainer, x, h, split, box_tflops=(box or {}).get("tflops_issued"))
-            except Exception as e:                                    # noqa: BLE001 -- diagnostics never touch the headline line
-                out["roofline"]["kernels"] = {"error": repr(e)}
-        if world == 1 and not args.no_extra:
-            out["f32_mode"] = f32_mode(dev, x, h)
-            out["other_models"] = other_models(dev)
-        if world == 1 and not args.no_cpu:
-            out["cpu_baseline"] = cpu_baseline()
+    if args.full:
+        full_report(out, args, wl, dev, use_dist, world, rank, dt_own, ms_per_step, barrier)
     if use_dist:
         dist.barrier()
         dist.destroy_process_group()

@@ -45,6 +45,17 @@ def test_plan_function_strips_launcher_flags():
     assert int(env["OMP_NUM_THREADS"]) >= 1
 
 
+def test_full_is_off_by_default_and_reaches_every_rank():
+    """A plain run measures the headline alone; `--full` and the --no-* flags that trim it go to the ranks as given."""
+    sys.path.insert(0, ROOT)
+    import bench
+    assert not bench.parse_args([]).full and bench.parse_args(["--full"]).full
+    r = _run("--gpus", "2", "--full", "--no-cpu", "--dry-run")
+    assert r.returncode == 0, r.stderr
+    cmd = json.loads(r.stdout.strip().splitlines()[-1])["cmd"]
+    assert cmd[cmd.index(BENCH) + 1:] == ["--gpus", "2", "--full", "--no-cpu"]
+
+
 def test_launcher_starts_ranks_and_relays_rank0_line():
     r = _run("--gpus", "2", "--steps", "4", "--warmup", "1", "--selftest", "ok")
     assert r.returncode == 0, r.stderr[-2000:]

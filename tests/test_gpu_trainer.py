@@ -322,3 +322,29 @@ def test_bench_dump_outputs_hold_the_last_step(dev, tmp_path, model):
     assert np.all(np.abs(got["logdet"] - logdet) <= 1e-4 * np.abs(logdet) + 1e-2)
     if wl["trainer"] is not None:
         assert np.array_equal(got["logged"], wl["trainer"].metrics.cpu().numpy())
+
+
+def test_bench_plain_run_is_the_headline_alone(dev, tmp_path):
+    """bench.py without --full: warm-up, timed steps, --dump-outputs and the line, nothing measured behind them.  With --full (its CPU,
+    synthesis, extra-model and box legs left out to keep the test short) the same command adds the dominant kernel's roofline with the
+    per-shape table and the Adam step."""
+    import json
+    import subprocess
+    import sys
+    bench = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "bench.py")
+
+    def run(*extra):
+        r = subprocess.run([sys.executable, bench, "--gpus", "1", "--steps", "2", "--warmup", "1", "--batch", "2"] + list(extra),
+                           stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-3000:]
+        return json.loads(r.stdout.strip().splitlines()[-1])
+    plain = run("--dump-outputs", str(tmp_path))
+    assert plain["metric"].startswith("audio samples/sec") and plain["unit"] == "samples/s" and plain["higher_is_better"] is True
+    assert plain["value"] > 0 and plain["ms_per_step"] > 0 and plain["dtype"].startswith("f32")
+    assert plain["steps"] == 2 and plain["warmup"] == 1 and np.isfinite(plain["loss"])
+    assert plain["dump_outputs"]["arrays"]["z"]["written"] > 0 and os.path.exists(os.path.join(str(tmp_path), "z.npy"))
+    full_only = {"roofline", "box", "comm", "adam_step_ms", "inverse_roofline", "f32_mode", "other_models", "cpu_baseline"}
+    assert not full_only & set(plain) and not [k for k in plain if k.startswith("inverse_khz")]
+    full = run("--full", "--no-cpu", "--no-extra", "--no-inverse", "--no-box")
+    assert full["roofline"]["launches_timed"] > 0 and full["roofline"]["kernels"]["kernels"] and full["adam_step_ms"] > 0
+    assert not {"box", "comm", "f32_mode", "other_models", "cpu_baseline"} & set(full) and "inverse_khz" not in full

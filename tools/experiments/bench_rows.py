@@ -1,4 +1,4 @@
-"""prints the per-shape table of a bench.py JSON line read from stdin (developer tool)"""
+"""prints the per-shape table of a `bench.py --full` JSON line read from stdin (developer tool)"""
 import json, sys
 d = json.loads(sys.stdin.read().strip().splitlines()[-1])
 print('%.2f ms/step  gate %.1f us  loss %.6f' % (d['ms_per_step'], d['roofline']['launch_ms'] * 1e3, d['loss']))

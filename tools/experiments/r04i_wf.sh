@@ -1,9 +1,10 @@
 R=$GRAFT_REPO_ROOT
 cd $R
-python bench.py --model waveflow --no-inverse --steps 6 --warmup 2 2>/dev/null | tail -1 > gpurun_out/r04i_wf_bench.json
+mkdir -p out
+python bench.py --full --model waveflow --no-inverse --steps 6 --warmup 2 2>/dev/null | tail -1 > out/r04i_wf_bench.json
 python - <<'PY'
 import json
-d=json.load(open('gpurun_out/r04i_wf_bench.json'))
+d=json.load(open('out/r04i_wf_bench.json'))
 print(d['ms_per_step'])
 k=d['roofline']['kernels']
 print('timed', k['timed_ms_per_step'])

@@ -7,8 +7,8 @@ for rep in 1 2; do
 python tools/experiments/infer_latency.py 63 2>&1 | grep "single call" >> $O
 WGFLOW_LIB=$R/variants/lib_t0.so python tools/experiments/infer_latency.py 63 2>&1 | grep "single call" >> $O
 done
-python bench.py --no-cpu --no-extra --steps 10 --warmup 3 2>/dev/null | tail -1 | python -c "
+python bench.py --full --no-cpu --no-extra --steps 10 --warmup 3 2>/dev/null | tail -1 | python -c "
 import json,sys; d=json.loads(sys.stdin.read()); print('new', d['ms_per_step'], d.get('inverse_khz_16128'), d.get('inverse_khz_220672'))" >> $O
-WGFLOW_LIB=$R/variants/lib_t0.so python bench.py --no-cpu --no-extra --steps 10 --warmup 3 2>/dev/null | tail -1 | python -c "
+WGFLOW_LIB=$R/variants/lib_t0.so python bench.py --full --no-cpu --no-extra --steps 10 --warmup 3 2>/dev/null | tail -1 | python -c "
 import json,sys; d=json.loads(sys.stdin.read()); print('old', d['ms_per_step'], d.get('inverse_khz_16128'), d.get('inverse_khz_220672'))" >> $O
 cat $O

@@ -2,7 +2,7 @@
 cd $GRAFT_REPO_ROOT
 {
 echo "=== parity (waveflow)"; timeout 900 python -m pytest tests/test_gpu_parity.py tests/test_gpu_trainer.py -x -q -k "wf or waveflow or wn2d" 2>&1 | grep -E "passed|failed|Error|assert" | tail -6
-for rep in 1 2; do python bench.py --model waveflow --steps 10 --warmup 3 --no-box --no-inverse 2>/dev/null | python tools/experiments/bench_rows.py | head -3; done
+for rep in 1 2; do python bench.py --full --model waveflow --steps 10 --warmup 3 --no-box --no-inverse 2>/dev/null | python tools/experiments/bench_rows.py | head -3; done
 cd /tmp && export TMPDIR=/tmp
 rocprofv3 --kernel-trace --stats --output-format csv -d $GRAFT_REPO_ROOT/gpurun_out/prof_r05r -- python3 $GRAFT_REPO_ROOT/bench.py --model waveflow --no-inverse --no-box --steps 3 --warmup 1 > /dev/null 2>&1
 cd $GRAFT_REPO_ROOT

@@ -11,4 +11,4 @@ for tag in ("a","b"):
     for r in list(csv.DictReader(open(f))):
         if any(k in r['Name'] for k in ('end_affine','mix_kernel<8','start_fwd','convlayer16g','wgrad16t')): print(tag, "%-60s %6s %9.2f us" % (r['Name'][:60], r['Calls'], float(r['AverageNs'])/1e3))
 PY
-python bench.py --steps 10 --warmup 3 --no-inverse 2>/dev/null | python tools/experiments/bench_rows.py | head -2
+python bench.py --full --steps 10 --warmup 3 --no-inverse 2>/dev/null | python tools/experiments/bench_rows.py | head -2

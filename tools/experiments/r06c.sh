@@ -4,7 +4,7 @@ python -m pytest tests -m gpu -x -q 2>&1 | tail -12 > gpurun_out/r06c_tests.txt
 cat gpurun_out/r06c_tests.txt
 for rep in 1 2; do for lrk in 0 1; do
   printf "WG_LOWRANK=%s " $lrk
-  WG_LOWRANK=$lrk python bench.py --steps 10 --warmup 3 --no-cpu --no-extra --no-box 2>/dev/null | python -c "
+  WG_LOWRANK=$lrk python bench.py --full --steps 10 --warmup 3 --no-cpu --no-extra --no-box 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 print('%.2f ms/step  inv16k %.0f  inv220k %.0f  batch8 %.0f  musicnet %.0f' % (d['ms_per_step'], d['inverse_khz_16128'], d['inverse_khz_220672'], d['inverse_khz_batch8x16128'], d.get('inverse_khz_musicnet_220672', 0)))

@@ -3,7 +3,7 @@ python -m pytest tests -m gpu -x -q 2>&1 | tail -5 > gpurun_out/r06j_tests.txt
 cat gpurun_out/r06j_tests.txt
 for rep in 1 2; do for lrk in 0 1; do
   printf "wsrglow WG_LOWRANK=%s " $lrk
-  WG_LOWRANK=$lrk python bench.py --model wsrglow --steps 10 --warmup 3 --no-box 2>/dev/null | python -c "
+  WG_LOWRANK=$lrk python bench.py --full --model wsrglow --steps 10 --warmup 3 --no-box 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 print('%.2f ms/step' % d['ms_per_step'])

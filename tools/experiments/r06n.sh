@@ -4,5 +4,5 @@ python -m pytest tests/test_gpu_parity.py -x -q -s -k "wide_batch or shape_sweep
 grep -E "passed|failed|FAILED" gpurun_out/r06n_tests.log | tail -3; grep -E "headline shape vs float64|WaveFlow 12 x 16000" gpurun_out/r06n_tests.log
 for rep in 1 2; do for sw in 0 1; do
   printf "WG_TW_FROM_GATE=%s " $sw
-  WG_TW_FROM_GATE=$sw python bench.py --steps 10 --warmup 3 --no-cpu --no-extra --no-inverse --no-box 2>/dev/null | python tools/experiments/bench_rows.py | head -5
+  WG_TW_FROM_GATE=$sw python bench.py --full --steps 10 --warmup 3 --no-cpu --no-extra --no-inverse --no-box 2>/dev/null | python tools/experiments/bench_rows.py | head -5
 done; done 2>&1 | tee gpurun_out/r06n_ab.txt

@@ -1,7 +1,7 @@
 # usage: bash tools/experiments/shape_ab.sh v1 v2 ...: per-shape conv / weight-gradient durations (bench.py's roofline.kernels) per variant library
 for v in "$@"; do
   echo "== $v"
-  WGFLOW_LIB=variants/lib_$v.so python bench.py --steps 3 --warmup 1 --no-cpu --no-extra --no-inverse 2>/dev/null | python -c "
+  WGFLOW_LIB=variants/lib_$v.so python bench.py --full --steps 3 --warmup 1 --no-cpu --no-extra --no-inverse 2>/dev/null | python -c "
 import sys,json
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 print('  step %.2f ms'%d['ms_per_step'])

@@ -56,7 +56,7 @@ def pmc_summary(tag, paths):
 def shape_summary(tag, bench_json):
     """python tools/profile_summary.py --shapes <tag> <bench line .json>: rocprofv3's kernel statistics lump every product that runs on one
     kernel instantiation into one row (convgemm16q_kernel<0, 2, 1> is the residual conv, the data-gradient conv, the skip product, the
-    conditioning gradient and the start / end convs); the per-SHAPE table comes from the bench line, whose `roofline.kernels` object times
+    conditioning gradient and the start / end convs); the per-SHAPE table comes from a `bench.py --full` line, whose `roofline.kernels` object times
     every conv / weight-gradient launch with HIP events and groups them by the (class, M, K) the library attaches to the launch
     (wg_timer_read_info).  Written as profiles/<tag>_shape_rooflines.csv."""
     d = json.loads(open(bench_json).read().strip().splitlines()[-1])
