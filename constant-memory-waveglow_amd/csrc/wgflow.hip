@@ -1314,8 +1314,10 @@ void run_convgemm(Ctx &cx, const Geo &g, const float *A, int lda, int M, const S
             // short is mostly this kernel's longer prologue; S-plane arrays and weight images beyond 4 GB: its 32-bit offsets)
             // a gate conv whose tiles cannot fill the chip, cut along K (WSRGlow: 64 tiles, 139 chunks -> 4 parts of 35 on 256 workgroups) --
             // the parts go to the workspace's slab (wn_ws_layout sizes it for this in every mode, so a plain forward and a training step's
-            // forward sum K in the same order; env WG_G192_SPLITK=0: off)
-            if (g192_on() && so_gate && g.rows == 0 && !cx.row_sel1 && !cx.rec && M % WGG_BM == 0 && g.H >= 64 && cus % 8 == 0 && cx.gslab &&
+            // forward sum K in the same order; env WG_G192_SPLITK=0: off).  Never a gate conv asked for its partial rows of `out`: the cut
+            // writes none, and the uncut kernels with the rows are the faster pass (WaveGlow-256 at 6 x 16 000, layers 1-7 of every WN
+            // cut and the end conv over the gate planes: 23.9 against 21.7 ms per step)
+            if (g192_on() && so_gate && !as.part && g.rows == 0 && !cx.row_sel1 && !cx.rec && M % WGG_BM == 0 && g.H >= 64 && cus % 8 == 0 && cx.gslab &&
                 g192_fits(as, a16.img_stride, nseg)) {
                 const int nct = (g.B * g.Tt + WGG_BN - 1) / WGG_BN, nrb = M / WGG_BM;
                 int nt, S;
@@ -2176,12 +2178,20 @@ static bool gate_parts_on(Ctx &cx, const WnRun &r)
     if (!lowrank_base(cx, r) || !gate_parts_shape(r.d) || !r.w.gpart_step || !r.L.effA || cx.probe) return false;
     if (env_sw().layer_fusion_big) return false;              // (the opt-in one-launch layer on 256 x 128 tiles has its own gate epilogue)
     GslabScope gslab_scope(cx, r, true);
-    int route = 0;
-    cx.probe = &route;
+    // every layer of the pass must take a route that writes the rows, and layer 0 is not routed like the others where the start is folded
+    // into it (start_fold_on: 6 chunks of K against 27 at 256 channels; the 256 x 192-tile kernel takes 16 chunks and more, and writes
+    // 8-float rows only).  Layers 1 .. depth-1 differ only in their dilation, which no routing rule reads (the tap shifts are segment
+    // offsets; g192_fits and the tile counts see K, M and the columns): layer 1 answers for all of them.
+    int route0 = 0, route1 = 1;
     cx.gate_eff = r.pk + r.L.effA; cx.gate_part = r.ws + r.w.gpart; cx.gate_prow = gate_part_prow(r.d);
+    cx.probe = &route0;
     wn_gate_conv(cx, r, 0, 0, true);
+    if (r.d.depth > 1) {
+        cx.probe = &route1;
+        wn_gate_conv(cx, r, 1, 1, true);
+    }
     cx.probe = nullptr; cx.gate_eff = nullptr; cx.gate_part = nullptr; cx.gate_prow = 8;
-    return route == 1;
+    return route0 == 1 && route1 == 1;
 }
 
 void wn_forward(Ctx &cx, const WnRun &r)

@@ -367,14 +367,19 @@ def test_full_size_properties(dev):
     with torch.no_grad():
         xr1, _ = m.reverse(z[5:6].detach().clone(), ht[5:6])
     assert float((xr1 - x[5:6]).abs().max()) < Z_ATOL
-    # linearity of the gradient in the batch: mean of two half-batch gradients == full-batch gradient (DP semantics)
-    m.zero_grad()
-    for sl in (slice(0, 12), slice(12, 24)):
-        zz, ll = m(x[sl].clone(), ht[sl])
-        (0.5 * crit(zz, ll)).backward()
-    for n, p in m.named_parameters():
-        a, b = p.grad, g_full[n]
-        assert float((a - b).abs().max()) <= GRAD_RTOL * float(b.abs().max()) + 1e-12, n
+    # linearity of the gradient in the batch: the mean of the shards' gradients == the full-batch gradient (DP semantics), at the per-rank
+    # shapes of batch 24 over 2, 4 and 8 GPUs: 12 x 16 000 (the 256 x 192-tile gate conv), 6 x 16 000 (layers 1-7 cut their gate conv
+    # along K), 3 x 16 000
+    for shards in (2, 4, 8):
+        m.zero_grad()
+        per = B // shards
+        for s in range(shards):
+            sl = slice(s * per, (s + 1) * per)
+            zz, ll = m(x[sl].clone(), ht[sl])
+            (crit(zz, ll) / shards).backward()
+        for n, p in m.named_parameters():
+            a, b = p.grad, g_full[n]
+            assert float((a - b).abs().max()) <= GRAD_RTOL * float(b.abs().max()) + 1e-12, (shards, n)
 
 
 @pytest.mark.parametrize("cname", ["d4", "last", "r5d3"])
@@ -690,6 +695,220 @@ def test_c2_full_batch_vs_oracle(dev, precision, request):
         assert abs(float(np.sqrt((dh.astype(np.float64) ** 2).sum())) - float(gold_ref["dh_norm"])) <= 1e-4 * float(gold_ref["dh_norm"])
         print("headline shape vs float64 oracle (memory_efficient=%s): |dz| %.2e, worst gradient %.2e of its tensor's max (%d oracle workers)"
               % (mem_eff, float(np.abs(npy(z) - ref["z"]).max()), worst, workers))
+
+
+# ---- the headline WN at the column counts where the gate conv changes kernel --------------------------------------------------------
+# 256 channels, depth 8, radix 3 over B x Tt columns (Tt = N / 8 rounded up to 128).  With the start folded into layer 0 (start_fold_on)
+# layer 0's gate conv is 6 chunks of K and layers 1-7's are 27, so the two are routed apart (csrc/wgflow.hip run_convgemm, 256 CUs):
+# fewer than 384 tiles of 128 x 128 take 128 x 64 tiles; the 256 x 192-tile kernel needs 16+ chunks and whole rounds to 10 %, the
+# 256 x 128 form to 17 %; gate_split_plan would cut 27 chunks (not 6) in two where 256 x 192 tiles number 128, but the cut writes no
+# partial rows of `out`, so it never takes a gate conv that is asked for them.  Every gate conv of a pass writes its rows, or none.
+ROUTE_CFG = dict(fill.CONFIGS["c2"], flows=3, n_early_every=1)      # flows over 8, 6 and 4 channels: the three WN shapes of c2
+GATE_Q1, GATE_Q2, GATE_Q22 = ("convgemm16q_kernel<EPI_GATE_SO, 1>", "convgemm16q_kernel<EPI_GATE_SO, 2>",
+                              "convgemm16q_kernel<EPI_GATE_SO, 2, 2>")
+GATE_G = "convgemm16g_kernel<EPI_GATE_SO>"
+
+
+def _oracle_workers(B):
+    """(workers, threads) for oracle/torch_cpu.py train_step_parallel on what this process may really use"""
+    from oracle import torch_cpu
+    n_allowed, quota, firsts = torch_cpu.host_cpu_budget()
+    cores = max(1, int(quota) if quota else len(firsts))
+    workers = max(1, min(B, cores // 2, torch_cpu.MAX_WORKERS))
+    return workers, max(1, min(8, cores // workers))
+
+
+def _launch_sites(fn):
+    """fn() under a timer on every kernel class: (its result, {(class, launch site as written there, parentheses dropped): launches})."""
+    import ctypes as C
+    from constant_memory_waveglow_amd import _lib
+    L = _lib.lib()
+    timer = L.wg_timer_create(-1, 4096)
+    L.wg_timer_attach(timer)
+    try:
+        out = fn()
+        torch.cuda.synchronize()
+    finally:
+        L.wg_timer_attach(None)
+    try:
+        n = L.wg_timer_count(timer)
+        info = (C.c_longlong * (5 * n))()
+        L.wg_timer_read_info(timer, info, n)
+        nb = C.create_string_buffer(256)
+        sites = {}
+        for i in range(n):
+            assert L.wg_timer_read_name(timer, i, nb, 256) >= 0
+            key = (int(info[5 * i]), nb.value.decode().strip("()"))
+            sites[key] = sites.get(key, 0) + 1
+    finally:
+        L.wg_timer_destroy(timer)
+    return out, sites
+
+
+def _gate_counters():
+    from constant_memory_waveglow_amd import _lib
+    L = _lib.lib()
+    return np.array([L.wg_stat_gate_part_launches(), L.wg_stat_gate_split_launches()])
+
+
+def _full_chip():
+    return torch.cuda.get_device_properties(0).multi_processor_count == 256      # (the routes above are derived for 256 CUs)
+
+
+def _assert_gate_routes(precision, sites, counts, passes, gate0, gate1, depth):
+    """`passes` WN passes ran: in each, layer 0's gate conv on gate0 and layers 1 .. depth-1 on gate1, every one writing its partial rows
+    of `out` and none cut along K (counts: wg_stat_gate_part_launches, wg_stat_gate_split_launches over the call)."""
+    from constant_memory_waveglow_amd import _lib
+    parts, cuts = (int(c) for c in counts)
+    named = [s for k, s in sites if k in (_lib.K_CONV_GATE, _lib.K_LAYER)]
+    if precision != SPLANE:                 # (no S-plane gate output in these modes: none of its kernels, nothing written, nothing cut)
+        assert parts == 0 and cuts == 0, (parts, cuts)
+        assert not any("_SO" in s or s.startswith(("convgemm16q_", "convgemm16g_", "convgemm16h_", "convlayer16")) for s in named), sites
+        return
+    if not _full_chip():
+        return
+    gate = {}
+    for (k, s), n in sites.items():
+        if k == _lib.K_CONV_GATE:
+            gate[s] = gate.get(s, 0) + n
+    want = {gate0: passes}
+    want[gate1] = want.get(gate1, 0) + (depth - 1) * passes
+    assert gate == want, sites
+    assert not any(k == _lib.K_LAYER for k, _ in sites), sites     # (convlayer16g_kernel takes 256 column tiles of 192 and more)
+    assert parts == depth * passes and cuts == 0, (parts, cuts)
+
+
+def _route_case(dev, precision, request, B, N, gate0, gate1, kept=False):
+    """One training step of ROUTE_CFG at B x N through FlowTrainer.step (wg_train_step, with dh) against the float64 oracle, the inverse
+    of the oracle's z at the same columns, and the gate conv kernels both ran (S-plane mode)."""
+    from oracle import torch_cpu
+    from constant_memory_waveglow_amd.parallel import FlowTrainer
+    cfg = ROUTE_CFG
+    F = -(-N // cfg["hop_size"])
+    tag = "route/%dx%d" % (B, N)
+    specs = fill.model_param_specs(cfg)
+    P = fill.fill_params(specs, tag + "/")
+    audio, h = fill.inputs(tag, B, N, F, cfg["n_mels"])
+    workers, threads = _oracle_workers(B)
+    ref = oracle_once(request, lambda: torch_cpu.train_step_parallel(
+        cfg, fill.table(specs, P), audio, h, fill.SIGMA, workers=workers, threads=threads, need_dh=True, double=True))
+    x, ht = T(audio, dev), T(h, dev)
+    for mem_eff in ((True, False) if kept else (True,)):
+        m = cm.WaveGlow(memory_efficient=mem_eff, bias=False, **cfg)
+        m.load_state_dict({k: torch.from_numpy(v) for k, v in P.items()})
+        m = m.to(dev)
+        tr = FlowTrainer(m, fill.SIGMA)
+        tr.want_dh = True
+        c0 = _gate_counters()
+        (loss, z, logdet), sites = _launch_sites(lambda: tr.step(x, ht))
+        counts = _gate_counters() - c0
+        assert np.abs(npy(z) - ref["z"]).max() < Z_ATOL, mem_eff
+        assert logdet_close(npy(logdet), ref["logdet"], N), mem_eff
+        assert abs(float(loss) - ref["loss"]) < LOSS_ATOL, mem_eff
+        named = dict(m.named_parameters())
+        for i, (n, _, _) in enumerate(specs):
+            assert relmax(npy(named[n].grad).astype(np.float64), ref["grads"][i]) < GRAD_RTOL, (mem_eff, n)
+        assert relmax(npy(tr.last_dh).astype(np.float64), ref["dh"]) < GRAD_RTOL, mem_eff
+        # the forward of every flow and the recompute of every flow but the one the forward left in the workspace (the recompute runs
+        # before that flow's backward opens its finalisation queue: it routes like the forward); forward only when stored
+        passes = cfg["flows"] + (cfg["flows"] - 1 if mem_eff else 0)
+        _assert_gate_routes(precision, sites, counts, passes, gate0, gate1, cfg["depth"])
+        del tr
+    # the inverse at the same columns, from the oracle's own z
+    c0 = _gate_counters()
+    with torch.no_grad():
+        (xr, ldr), sites = _launch_sites(lambda: m.reverse(T(ref["z"].astype(np.float32), dev), ht))
+    counts = _gate_counters() - c0
+    assert np.abs(npy(xr) - audio).max() < Z_ATOL
+    assert logdet_close(-npy(ldr), ref["logdet"], N)
+    _assert_gate_routes(precision, sites, counts, cfg["flows"], gate0, gate1, cfg["depth"])
+
+
+def test_c2_wn_at_the_fused_skip_bar_vs_oracle(dev, precision, request):
+    """2 x 16 000 = 4 096 columns, WG_FUSED_SKIP_MIN_COLS exactly: the smallest shape with the one-product skip path, its rank-2ic form
+    with the partial rows and the S-plane-only residual stream at 256 channels.  128 tiles of 128 x 128: every gate conv on 128 x 64 tiles."""
+    _route_case(dev, precision, request, 2, 16000, GATE_Q1, GATE_Q1)
+
+
+def test_c2_wn_where_the_gate_conv_could_be_cut_along_k_vs_oracle(dev, precision, request):
+    """6 x 16 000 = 12 288 columns (the headline batch over 4 GPUs): 128 tiles of 256 x 192 fill half the CUs, where layers 1-7's gate
+    conv (27 chunks, not layer 0's 6) qualifies for the cut along K -- which writes no partial rows.  Every layer must keep the rows, on
+    128 x 128 tiles.  Both memory modes."""
+    _route_case(dev, precision, request, 6, 16000, GATE_Q2, GATE_Q2, kept=True)
+
+
+def test_c2_wn_at_the_cut_shape_with_a_partial_column_tile_vs_oracle(dev, precision, request):
+    """5 x 19 200 = 12 160 columns: the same shape for the cut with a partial last column tile (63.3 tiles of 192) and tiles that straddle
+    items; 380 tiles of 128 x 128 (under the 384 bar): every layer on 128 x 64 tiles."""
+    _route_case(dev, precision, request, 5, 19200, GATE_Q1, GATE_Q1)
+
+
+def test_c2_wn_gate_conv_on_one_round_of_192_column_tiles_vs_oracle(dev, precision, request):
+    """12 x 16 000 = 24 576 columns (batch 24 over 2 GPUs): layers 1-7 on 256 tiles of 256 x 192 -- one round -- writing the partial rows;
+    layer 0 (under 16 chunks) on 128 x 128 tiles, 1.5 rounds of the 256 x 128 form being too ragged."""
+    _route_case(dev, precision, request, 12, 16000, GATE_Q2, GATE_G)
+
+
+def test_c2_wn_gate_conv_on_two_rounds_of_shared_b_tiles_vs_oracle(dev, precision, request):
+    """16 x 16 000 = 32 768 columns: 171 column tiles of 192 leave too ragged a second round, so every layer runs 256 x 128 tiles in
+    exactly two rounds (convgemm16q_kernel<.., MG = 2>), with the partial rows."""
+    _route_case(dev, precision, request, 16, 16000, GATE_Q22, GATE_Q22)
+
+
+def _synthesis_round_trip(m, cfg, dev, tag, F):
+    """infer, then forward and reverse of one utterance of F frames: (the three calls' gate counters, N); asserts the round trip"""
+    N = F * cfg["hop_size"]
+    audio, h = fill.inputs(tag, 1, N, F, cfg["n_mels"])
+    x, ht = T(audio, dev), T(h, dev)
+    with torch.no_grad():
+        c0 = _gate_counters()
+        torch.manual_seed(0)
+        y = m.infer(ht[0], sigma=0.6)
+        c1 = _gate_counters()
+        z, ld = m(x, ht)
+        c2 = _gate_counters()
+        xr, ldr = m.reverse(z, ht)
+        counts = [c1 - c0, c2 - c1, _gate_counters() - c2]
+    assert y.shape == (N,) and bool(torch.isfinite(y).all())
+    assert np.abs(npy(xr) - audio).max() < Z_ATOL
+    assert logdet_close(-npy(ldr), npy(ld), N)
+    return counts
+
+
+@pytest.mark.parametrize("F", [376, 377, 384, 385])
+def test_c2_synthesis_at_the_cut_gate_conv_lengths(dev, precision, F):
+    """The full c2 model on one utterance of 376 / 377 / 384 / 385 mel frames (12 032 / 12 160 / 12 288 / 12 416 columns):
+    377-384 are where layers 1-7's gate conv qualifies for the cut along K, the other two lie outside that window.  infer gives F x 256
+    finite samples; forward then reverse gives the audio back and the logdets cancel; in each of the three calls every gate conv of
+    every WN writes its partial rows and none is cut."""
+    m, cfg, specs, P = build("c2", dev)
+    m.eval()
+    counts = _synthesis_round_trip(m, cfg, dev, "c2synth%d" % F, F)
+    for c in counts:
+        if precision != SPLANE:
+            assert tuple(c) == (0, 0), counts
+        elif _full_chip():
+            assert tuple(c) == (cfg["flows"] * cfg["depth"], 0), counts
+
+
+def test_musicnet_synthesis_at_192_frames(dev, precision):
+    """SWEEP's musicnet architecture (18 flows of depth 4, hop 512) on one utterance of 192 frames: 12 288 columns as above, with a halo
+    of 8 (g.H = 16) that keeps every product off the 256 x 192-tile kernels and the cut; every gate conv writes its partial rows."""
+    c = SWEEP[7]
+    cfg = dict(flows=c["flows"], n_group=c["n_group"], n_early_every=c["n_early_every"], n_early_size=c["n_early_size"],
+               hop_size=c["hop_size"], n_mels=c["n_mels"], dilation_channels=c["ch"][0], residual_channels=c["ch"][1],
+               skip_channels=c["ch"][2], depth=c["depth"], radix=c["radix"])
+    specs = fill.model_param_specs(cfg)
+    P = fill.fill_params(specs, "sweep7/")
+    m = cm.WaveGlow(memory_efficient=True, bias=False, **cfg)
+    m.load_state_dict({k: torch.from_numpy(v) for k, v in P.items()})
+    m = m.to(dev).eval()
+    counts = _synthesis_round_trip(m, cfg, dev, "musicnet192", 192)
+    for c in counts:
+        if precision != SPLANE:
+            assert tuple(c) == (0, 0), counts
+        elif _full_chip():
+            assert tuple(c) == (cfg["flows"] * cfg["depth"], 0), counts
 
 
 @pytest.mark.parametrize("c", [2, 4, 8])
