@@ -96,18 +96,7 @@ struct Ctx {
     float *gslab = nullptr;          // set inside wn_forward when the workspace has a weight-gradient slab (idle during a forward pass):
     size_t gslab_floats = 0;         // scratch for the K parts of a split gate conv (convgemm16g_kernel<WGG_EPI_PART>)
     struct StageRec *rec = nullptr;  // set while a launch sequence is RECORDED for the stage interpreter (wg_stage.h): nothing is launched
-    struct BigCap *cap = nullptr;    // set while run_convgemm only DESCRIBES a chip-filling launch (run_convlayer_big): nothing is launched
-    // the gate conv's share of WN's `out` from its own epilogue (ConvGemm16sArgs::part; wn_forward sets these around a layer's gate conv):
-    const float *gate_eff = nullptr; // Weff of the layer as A fragments (WnPack::effA)
-    float *gate_part = nullptr;      // that layer's partial rows
-    int gate_prow = 8;               // floats per row (gate_part_prow)
-    int part_written = 0;            // gate convs of this call that were launched with them
-    int *probe = nullptr;            // set while run_convgemm only REPORTS whether a gate conv would take the kernel that writes them (1) or not (0)
-};
-// a launch of the 256 x 128-tile conv kernel as its argument block (ntx x nty x ntz tiles of 256 rows), instead of the launch
-struct BigCap {
-    ConvGemm16sArgs as;
-    bool ok;
+    int part_written = 0;            // gate convs of this call launched with their partial rows of WN's `out` (ConvOp::part)
 };
 // the launches of one row step of WaveFlow's inverse, as argument blocks (see wg_stage.h); ok = false: a launch that the interpreter
 // cannot run turned up (the caller then launches everything the ordinary way)
@@ -131,7 +120,6 @@ thread_local const char *g_last_launch = "";
 #define WG_LAUNCH(ctx, kern, grid, block, shmem, ...)                         \
     do {                                                                      \
         if ((ctx).rec) (ctx).rec->ok = false;   /* not a recordable launch */ \
-        else if ((ctx).probe) { }               /* a route is being asked for, nothing runs */ \
         else if ((ctx).err == 0) {                                            \
             g_last_launch = #kern;                                            \
             hipLaunchKernelGGL(kern, grid, block, shmem, (ctx).st, __VA_ARGS__); \
@@ -208,9 +196,7 @@ struct WnD {
 // (2^-17 relative) now accumulates along the 8 layers of a WN instead of being refreshed from an exact fp32 chain.
 inline bool s_only_chain(const Ctx &cx, const WnD &d)
 {
-#if !defined(WG_OPT_NO_S_ONLY) && !defined(WG_OPT_MFMA32) && !defined(WG_OPT_NO_WSPEC) && !defined(WG_OPT_DMA)
-    // (only convgemm16q / convgemm16h read the accumulate-into value from an S-plane -- ConvGemm16sArgs::saux --: the superseded
-    // kernels of the A/B builds ignore it and would lose the residual term)
+#if !defined(WG_OPT_NO_S_ONLY)
 #if defined(WG_OPT_S_ONLY_1D)                               // A/B build: WN2D keeps its fp32 residual planes (before round 6's last commits)
     return cx.prec == 2 && !d.mode2d;
 #else
@@ -1143,346 +1129,352 @@ static bool g192_fits(const ConvGemm16sArgs &as, size_t img_stride, int nseg)
 // env WG_G192=0: the conv products never take the 256 x 192-tile kernel of wg_gemm16g.h (A/B runs in one build; EnvSw)
 static bool g192_on() { return env_sw().g192; }
 
-void run_convgemm(Ctx &cx, const Geo &g, const float *A, int lda, int M, const SegSpec *segs, int nseg, int epi,
-                  PRef out0, PRef out1, PRef out2, PRef aux0, PRef aux1, int nsplit, int accumulate, SRef s0 = snull(), SRef saux = snull())
+// A conv product as asked: the operands and epilogue of run_convgemm and, for a gate conv whose WN's end conv reads them, the partial rows
+// of `out` its epilogue should leave (ConvGemm16sArgs::eff / part / prow; part == nullptr: none asked for)
+struct ConvOp {
+    Geo g;
+    const float *A;
+    int lda, M, nseg, epi, nsplit, accumulate;
+    SegSpec seg[WG_MAX_SEG];
+    PRef out0, out1, out2, aux0, aux1;
+    SRef s0, saux;
+    const float *eff = nullptr;   // Weff of the layer as A fragments (WnPack::effA)
+    float *part = nullptr;        // that layer's partial rows
+    int prow = 8;                 // floats per row (gate_part_prow)
+    long long ksum() const { long long k = 0; for (int s = 0; s < nseg; ++s) k += seg[s].nch; return k; }
+    int chunks() const { int n = 0; for (int s = 0; s < nseg; ++s) n += (seg[s].nch + WG16_BK - 1) / WG16_BK; return n; }
+};
+ConvOp conv_op(const Geo &g, const float *A, int lda, int M, const SegSpec *segs, int nseg, int epi, PRef out0, PRef out1, PRef out2,
+               PRef aux0, PRef aux1, int nsplit, int accumulate, SRef s0 = snull(), SRef saux = snull())
 {
-    ConvGemmArgs a;
-    memset(&a, 0, sizeof(a));
-    a.A = A; a.lda = lda; a.M = M; a.nseg = nseg;
-    for (int s = 0; s < nseg; ++s) {
-        a.seg[s].src = segs[s].src; a.seg[s].Cp = segs[s].Cp; a.seg[s].ch0 = segs[s].ch0;
-        a.seg[s].nch = segs[s].nch; a.seg[s].shift = segs[s].shift;
-        a.seg[s].row_off = segs[s].row_off; a.seg[s].per_item = segs[s].per_item;
+    ConvOp op;
+    op.g = g; op.A = A; op.lda = lda; op.M = M; op.nseg = nseg; op.epi = epi; op.nsplit = nsplit; op.accumulate = accumulate;
+    std::copy(segs, segs + nseg, op.seg);
+    op.out0 = out0; op.out1 = out1; op.out2 = out2; op.aux0 = aux0; op.aux1 = aux1; op.s0 = s0; op.saux = saux;
+    return op;
+}
+
+// the kernel families a conv product can take (ConvRoute::kern); with the epilogue template argument (ConvRoute::epi) one instantiation: ck
+enum {
+    CK_F32, CK_16, CK_16_MT4,   // convgemm_kernel (exact fp32); convgemm16_kernel on 128 x 128 / 256 x 128 tiles (bf16x3, split on the fly)
+    CK_Q1, CK_Q2, CK_Q_M64,     // convgemm16q_kernel (bf16x3 from S-planes) on 128 x 64 / 128 x 128 / 64 x 128 tiles
+    CK_Q_CG2, CK_Q_MG2,         // convgemm16q_kernel on 128 x 256 tiles (two compute groups share A) / 256 x 128 tiles (they share B)
+    CK_H, CK_G, CK_G_SPLIT,     // convgemm16h_kernel (64 x 64 tiles); convgemm16g_kernel (256 x 192); that cut along K + gate_finish16g_kernel
+};
+constexpr int ck(int kern, int epi) { return kern * 16 + epi; }
+// how a conv product runs (route_conv), all that launch_conv needs to issue it
+struct ConvRoute {
+    int kern = CK_F32, epi = EPI_STORE;
+    dim3 grid, block;
+    ConvGemm16sArgs as;           // the argument block (precision 1 launches img, img_stride and c of it; precision 0 c alone)
+    bool part = false;            // the epilogue leaves the gate conv's partial rows of `out`
+    int S = 0, nt = 0;            // CK_G_SPLIT: K parts, 256 x 192 tiles per part
+    int err = 0;                  // WG_EINVAL: the product cannot run as asked (nothing is launched)
+};
+
+// What every route starts from: the argument block on 128 x 128 tiles, the grid of those tiles, and the error of a malformed product
+static ConvRoute conv_args(const Ctx &cx, const ConvOp &op)
+{
+    const Geo &g = op.g;
+    ConvRoute rt;
+    ConvGemm16sArgs &as = rt.as;
+    memset(static_cast<void *>(&as), 0, sizeof(as));
+    ConvGemmArgs &a = as.c;
+    a.A = op.A; a.lda = op.lda; a.M = op.M; a.nseg = op.nseg;
+    for (int s = 0; s < op.nseg; ++s) {
+        const SegSpec &sp = op.seg[s];
+        a.seg[s].src = sp.src; a.seg[s].Cp = sp.Cp; a.seg[s].ch0 = sp.ch0; a.seg[s].nch = sp.nch; a.seg[s].shift = sp.shift;
+        a.seg[s].row_off = sp.row_off; a.seg[s].per_item = sp.per_item;
     }
-    a.g = g; a.epi = epi; a.nsplit = nsplit; a.accumulate = accumulate;
-    a.out0 = out0; a.out1 = out1; a.out2 = out2; a.aux0 = aux0; a.aux1 = aux1;
-    const int mrows = epi == EPI_GATE ? M : M;
-    dim3 grid(g.Tt / WG_TILE, rup(mrows, WG_TILE) / WG_TILE, g.B), block(256);
+    a.g = g; a.epi = op.epi; a.nsplit = op.nsplit; a.accumulate = op.accumulate;
+    a.out0 = op.out0; a.out1 = op.out1; a.out2 = op.out2; a.aux0 = op.aux0; a.aux1 = op.aux1;
+    rt.grid = dim3(g.Tt / WG_TILE, rup(op.M, WG_TILE) / WG_TILE, g.B);
+    rt.block = dim3(256);
     if (cx.row_sel1) {
-        if (g.rows <= 0) { if (!cx.err) cx.err = WG_EINVAL; return; }
+        if (g.rows <= 0) { rt.err = WG_EINVAL; return rt; }
         a.row_sel1 = cx.row_sel1;
-        grid.z = g.B / g.rows;
+        rt.grid.z = g.B / g.rows;
+    }
+    if (!cx.prec) return rt;
+    as.img = mat_img(op.A, (int)op.ksum(), op.lda);
+    as.img_stride = (size_t)op.chunks() * op.lda * WG16_BK;
+    if (cx.prec == 1) return rt;
+    const SegSpec *segs = op.seg;
+#if !defined(WG_OPT_NO_TAP_IL)
+    {   // leading segments that are taps of one plane: walked interleaved (ConvGemm16sArgs::tap_il)
+        int nt = 1;
+        while (nt < op.nseg && segs[nt].s == segs[0].s && segs[nt].nch == segs[0].nch && segs[nt].sCp == segs[0].sCp &&
+               segs[nt].sch0 == segs[0].sch0 && segs[nt].per_item == segs[0].per_item) ++nt;
+        if (nt >= 2 && segs[0].s && segs[0].nch % WG16_BK == 0) { as.tap_il = nt; as.tap_chunks = segs[0].nch / WG16_BK; }
+    }
+#endif
+    as.s0 = op.s0; as.saux = op.saux; as.prow = op.prow;
+    if (op.epi == EPI_GATE && op.part && (size_t)(op.M / 64) * 1024 <= WGG_EFF_BYTES) { as.eff = op.eff; as.part = op.part; }
+    for (int s = 0; s < op.nseg; ++s) {
+        as.sseg[s].hi = (const unsigned short *)segs[s].s;
+        as.sseg[s].lo_off = (size_t)(segs[s].per_item ? g.B / g.rows : g.B) * segs[s].sCp * g.P;
+        as.sseg[s].Cp = segs[s].sCp; as.sseg[s].ch0 = segs[s].sch0;
+        as.sseg[s].row_off = segs[s].row_off; as.sseg[s].per_item = segs[s].per_item;
+        if (!segs[s].s) rt.err = WG_EINVAL;
+        if ((segs[s].row_off || segs[s].per_item) && g.rows <= 0) rt.err = WG_EINVAL;
+    }
+    return rt;
+}
+
+// fewer 128 x 128 tiles than 3/4 of the workgroup slots: the S-plane kernels take 128 x 64 tiles
+static bool conv_small(const ConvOp &op, const dim3 &grid)
+{
+    bool small = grid.x * grid.y * grid.z < 384;
+#if defined(WG_OPT_NI1_MASK)                      // experiment: 128 x 64 tiles (twice the tiles: a fuller last round) for a class of launches
+    const int epi = op.epi;
+    const long long Ksum = op.ksum();
+    if ((WG_OPT_NI1_MASK & 1) && epi == EPI_STORE && Ksum <= 256) small = true;
+    if ((WG_OPT_NI1_MASK & 2) && epi == EPI_DGATE) small = true;
+    if ((WG_OPT_NI1_MASK & 4) && epi == EPI_STORE && Ksum >= 1024 && Ksum < 2048) small = true;
+    if ((WG_OPT_NI1_MASK & 8) && epi == EPI_STORE && Ksum >= 2048) small = true;
+#else
+    (void)op;
+#endif
+    return small;
+}
+
+// Which kernel, tiles and grid a conv product takes.  Launches nothing and changes nothing, so that whoever needs the decision without
+// the launch (gate_parts_on) gets it from the same rules as launch_conv.
+ConvRoute route_conv(const Ctx &cx, const ConvOp &op)
+{
+    ConvRoute rt = conv_args(cx, op);
+    const Geo &g = op.g;
+    const int M = op.M, epi = op.epi, nseg = op.nseg;
+    const dim3 grid = rt.grid;
+    ConvGemm16sArgs &as = rt.as;
+    const ConvGemmArgs &a = as.c;
+    auto pick = [&](int kern, int e, dim3 gr, int threads) {
+        rt.kern = kern; rt.epi = e; rt.grid = gr; rt.block = dim3(threads);
+        rt.part = e == EPI_GATE_SO && as.part;
+        return rt;
+    };
+    if (rt.err || !cx.prec) return pick(CK_F32, epi, grid, 256);
+    if (cx.prec == 1) {
+        if (rup(M, WG_TILE) % 256 == 0) return pick(CK_16_MT4, epi, dim3(g.Tt / WG_TILE, rup(M, WG_TILE) / 256, g.B), 512);      // 256-row tiles when M allows it
+        return pick(CK_16, epi, grid, 256);
+    }
+    // persistent launch: one workgroup per resident slot (two per CU), each walking its share of the tile grid -- see the
+    // kernel; the gate backward stays at one workgroup per tile.  -DWG_OPT_NO_PERSIST: one workgroup per tile everywhere.
+    const int cus = device_cus();
+    const bool small = conv_small(op, grid);
+    as.ntx = small ? (int)grid.x * 2 : (int)grid.x; as.nty = (int)grid.y; as.ntz = (int)grid.z;
+    const int ntiles = as.ntx * as.nty * as.ntz;
+    int slots = epi == EPI_DGATE ? ntiles : 2 * cus;
+#if defined(WG_OPT_NO_PERSIST)
+    slots = ntiles;
+#endif
+    const dim3 gp = epi == EPI_DGATE ? dim3(as.ntx, as.nty, as.ntz) : dim3(std::min(ntiles, slots));
+    // plane rows dealt to XCDs (ConvGemm16sArgs::xcd_items): full persistent grids whose plane rows divide by the 8 XCDs
+    const bool xcd_rows = epi != EPI_DGATE && as.ntz % 8 == 0 && g.rows == 0
+#if defined(WG_OPT_NO_XCD_ROWS)
+                          && false
+#endif
+        ;
+    if (xcd_rows && ntiles >= slots && slots % 8 == 0) as.xcd_items = as.ntz / 8;
+#if !defined(WG_OPT_NO_XCD_COLS)
+    // XCD columns (ConvGemm16sArgs::xcd_items < 0): full persistent grids whose plane rows do NOT divide by the 8 XCDs
+    // (measured, WSRGlow at batch 12: the conditioning gradient -- 29 row tiles -- 516.9 -> 478.6 us; launches with few row tiles do not
+    // gain -- the gate conv, 4 row tiles: 107.6 -> 109.3 us -- so the order is used from 8 row tiles on)
+    else if (epi != EPI_DGATE && g.rows == 0 && !cx.row_sel1 && ntiles >= slots && slots % 8 == 0 && as.ntx * as.ntz >= 8 && as.nty >= 8) as.xcd_items = -1;
+#endif
+#if !defined(WG_OPT_NO_HTILE)
+    // at most half as many 128 x 64 tiles as CUs (one utterance being synthesised, WaveFlow's row-by-row inverse): such a launch
+    // is as long as its slowest CU needs to take in its operands -- 64 x 64 tiles, twice the workgroups (wg_gemm16h.h)
+    // (measured and not adopted: also where the 128 x 64 tiles are 1 - 1.5 per CU -- WSRGlow's gate conv, 384 such tiles --
+    // three 64 x 64 tiles on every CU instead: 52.9 against 50.5 ms per WSRGlow step)
+    // (measured slower in round 5: the same tiles with the operands by LDS-DMA into a ring of eight chunk buffers, seven chunks in
+    // flight, four waves that multiply and issue -- git show 4c099e9:tools/experiments/wg_gemm16m.h: 2.70 against 2.46-2.52 ms per 0.7 s utterance,
+    // WaveFlow's row-by-row synthesis 96.6 against 86.7 ms: a CU's intake rate, not the depth of its prefetch, bounds these launches)
+    // (2 or 4 k-steps per chunk and barrier measured slower: git show 4c099e9:tools/experiments/wg_gemm16hk.h)
+    if (small && 2 * ntiles <= cus && epi != EPI_DGATE) {
+        as.nty = 2 * (int)grid.y;
+        return pick(CK_H, epi, dim3(as.ntx * as.nty * as.ntz), 512);
+    }
+#endif
+    // the instantiations with hand-issued epilogues: S-plane-only stores (no fp32 output, no fp32 accumulate-into plane), the S-plane-only
+    // gate and gate backward, and stores to an fp32 plane only
+    int te = epi;
+#if !defined(WG_OPT_NO_EPI_BATCH)
+    if (epi == EPI_STORE && as.s0.hi && !a.out0.p && !a.aux0.p) te = EPI_STORE_SO;
+    else if (epi == EPI_GATE && as.s0.hi && !a.out0.p && WG_TS_INTERLEAVED) te = EPI_GATE_SO;
+    else if (epi == EPI_DGATE && as.s0.hi && !a.out0.p && WG_TS_INTERLEAVED) te = EPI_DGATE_SO;
+    else if (epi == EPI_STORE && !as.s0.hi && a.out0.p && !as.saux.hi) te = EPI_STORE_FO;
+#endif
+    const bool so_gate = te == EPI_GATE_SO;
+#if !defined(WG_OPT_NO_G192)
+    // 256 x 192 tiles over flattened columns, eight multiplying waves fed by LDS-DMA (wg_gemm16g.h): the S-plane-only gate conv and
+    // store / data-gradient / skip products whose tiles deal out evenly over the CUs (env WG_G192=0 restores the 256 x 128 / 128 x 128 forms)
+    // (products of fewer than 16 chunks -- the residual conv, K = 256: 36.6 against 35.3 us -- stay on the older kernel: a tile that
+    // short is mostly this kernel's longer prologue; S-plane arrays and weight images beyond 4 GB: its 32-bit offsets)
+    // a gate conv whose tiles cannot fill the chip, cut along K (WSRGlow: 64 tiles, 139 chunks -> 4 parts of 35 on 256 workgroups) --
+    // the parts go to the workspace's slab (wn_ws_layout sizes it for this in every mode, so a plain forward and a training step's
+    // forward sum K in the same order; env WG_G192_SPLITK=0: off).  Never a gate conv asked for its partial rows of `out`: the cut
+    // writes none, and the uncut kernels with the rows are the faster pass (WaveGlow-256 at 6 x 16 000, layers 1-7 of every WN
+    // cut and the end conv over the gate planes: 23.9 against 21.7 ms per step)
+    const int nc = op.chunks();
+    if (g192_on() && so_gate && !as.part && g.rows == 0 && !cx.row_sel1 && !cx.rec && M % WGG_BM == 0 && g.H >= 64 && cus % 8 == 0 && cx.gslab &&
+        g192_fits(as, as.img_stride, nseg)) {
+        int nt, S;
+        gate_split_plan(g.B * g.Tt, M, nc, cus, nt, S);
+        if (env_sw().g192_splitk && S && (size_t)S * nt * 8 * 24 * 256 <= cx.gslab_floats) {
+            as.ntx = (g.B * g.Tt + WGG_BN - 1) / WGG_BN; as.nty = M / WGG_BM; as.ntz = S; as.xcd_items = 2;
+            rt.S = S; rt.nt = nt;
+            return pick(CK_G_SPLIT, WGG_EPI_PART, dim3(cus), 512);
+        }
+    }
+    const bool fo_g = te == EPI_STORE_FO && !a.aux0.p;   // (the skip sum: fp32 plane out, nothing to accumulate into)
+    if (g192_on() && !small && (so_gate || te == EPI_STORE_SO || fo_g) && g.rows == 0 && !cx.row_sel1 && !cx.rec && M % WGG_BM == 0 && g.H >= 64 &&
+        cus % 8 == 0 && nc >= 16 && nc <= WGG_MAXCHUNKS && g192_fits(as, as.img_stride, nseg)) {
+        const int nct = (g.B * g.Tt + WGG_BN - 1) / WGG_BN, nrb = M / WGG_BM, nt = nct * nrb;
+        const int rounds = (nt + cus - 1) / cus;
+        if (nt >= cus && (double)(rounds * cus - nt) <= 0.1 * rounds * cus) {
+            as.ntx = nct; as.nty = nrb; as.ntz = 1; as.xcd_items = 0;
+            if (env_sw().g192_own) as.xcd_items = 1;                                   // experiment: column ownership
+            if (as.prow != 8) as.part = nullptr;      // (this kernel's epilogue writes 8-float rows)
+            return pick(CK_G, te, dim3(cus), 512);
+        }
+    }
+#endif
+#if !defined(WG_OPT_NO_M64)
+    // products with at most 64 rows on 64 x 128 tiles (convgemm16q_kernel<.., M64>): WaveFlow's 64-channel WN2D -- on 128-row tiles
+    // half of every MFMA multiplied padding (the data-gradient conv: 181 TF against 314 for the full-height gate conv)
+    if (!small && M <= 64 && epi != EPI_GATE && epi != EPI_RESSKIP) return pick(CK_Q_M64, te, gp, 512);
+#endif
+    if (small) return pick(CK_Q1, te, gp, 512);
+#if !defined(WG_OPT_NO_CG2)
+    // products with ONE 128-row tile (WaveFlow's gate conv, M = 2 Cd = 128) on 128 x 256 tiles: one 16-wave workgroup per CU whose two
+    // compute groups share the A image of every chunk (convgemm16q_kernel<.., CG2>) -- 25 % less L2 -> LDS traffic for a launch
+    // that sits at the per-CU intake limit
+    if (epi == EPI_GATE && (int)grid.y == 1 && g.Tt % 256 == 0 && cus % 8 == 0) {
+        const int nt2 = (int)grid.x / 2 * as.nty * as.ntz;
+        if (nt2 >= cus) {
+            as.ntx = (int)grid.x / 2; as.xcd_items = 0;
+            return pick(CK_Q_CG2, te, dim3(std::min(nt2, cus)), 1024);
+        }
+    }
+#endif
+#if !defined(WG_OPT_NO_MG2)
+    // 256 x 128 tiles, one 16-wave workgroup per CU (the compute groups share every chunk's B image: 25 % less L2 -> LDS
+    // traffic, no slower co-resident workgroup left to finish alone): gate conv 125.7 -> 118.6 us.  Only where the tiles deal out
+    // evenly over the CUs: at 1.5 tiles per CU (the 256-row products of the training shape: 384 such tiles) the half-empty second
+    // round costs more than the sharing saves (measured: step 81.8 -> 83.0 ms with every eligible launch on this path).
+    // (1.69 such tiles per CU -- the gate conv of a 10 s utterance -- still gain 4 %: 20.2 -> 21.0 MHz; 1.5 per CU lose)
+    const int rounds = (ntiles / 2 + cus - 1) / cus;
+    const bool mg2_ok = ntiles / 2 >= cus && (double)(rounds * cus - ntiles / 2) <= 0.17 * rounds * cus;
+    if (epi != EPI_DGATE && rup(M, WG_TILE) % 256 == 0 && mg2_ok) {
+        as.nty = (int)grid.y / 2;
+        if (cus % 8) as.xcd_items = 0;                // (mg2_ok: at least one tile per CU)
+        return pick(CK_Q_MG2, te, dim3(std::min(ntiles / 2, cus)), 1024);
+    }
+#endif
+    return pick(CK_Q2, te, gp, 512);
+}
+
+// The one place a conv product is issued: its timer, the kernel(s) of its route, the counters of partial rows and K cuts.  While a call
+// is recorded for WaveFlow's row walk (Ctx::rec), the 64 x 64-tile route is appended to the recording instead -- the stage interpreter
+// runs convgemm16h_body on its argument block -- and any other route makes the recording unusable.
+void launch_conv(Ctx &cx, const ConvOp &op, const ConvRoute &rt)
+{
+    if (rt.err) { if (!cx.err) cx.err = rt.err; return; }
+    const ConvGemm16sArgs &as = rt.as;
+    if (cx.rec) {
+        if (rt.kern == CK_H) cx.rec->add(op.epi == EPI_STORE ? WGS_CONV_STORE : op.epi == EPI_GATE ? WGS_CONV_GATE : WGS_CONV_RESSKIP, (int)rt.grid.x).u.conv = as;
+        else cx.rec->ok = false;
+        return;
     }
     // what this launch has to move at least: every distinct source plane once (hi + lo bf16, or fp32), the weights, the outputs and
     // auxiliary planes of its epilogue (fp32 planes 4 B, S-planes 2 + 2 B per element)
-    long long Ksum = 0, in_ch = 0;
-    for (int s = 0; s < nseg; ++s) {
-        Ksum += segs[s].nch;
+    const Geo &g = op.g;
+    const int M = op.M, epi = op.epi;
+    const SegSpec *segs = op.seg;
+    long long in_ch = 0;
+    for (int s = 0; s < op.nseg; ++s) {
         bool seen = false;
         for (int u = 0; u < s; ++u) seen = seen || (segs[u].src == segs[s].src && segs[u].s == segs[s].s && segs[u].ch0 == segs[s].ch0);
         if (!seen) in_ch += segs[s].nch;
     }
-    const long long cols = (long long)(cx.row_sel1 && g.rows > 0 ? g.B / g.rows : g.B) * g.T;
+    const long long Ksum = op.ksum(), cols = (long long)(cx.row_sel1 && g.rows > 0 ? g.B / g.rows : g.B) * g.T;
     long long out_ch = 0;
-    if (epi == EPI_GATE) out_ch = (long long)(M / 2) * ((out0.p ? 1 : 0) + (out1.p ? 2 : 0) + (s0.hi ? 1 : 0));
-    else if (epi == EPI_DGATE) out_ch = (long long)M * 2 /* tanh, sigmoid in */ + 2LL * M * ((s0.hi ? 1 : 0) + (out0.p ? 1 : 0));
-    else if (epi == EPI_RESSKIP) out_ch = (long long)nsplit * (1 + (out0.p ? 1 : 0) + (s0.hi ? 1 : 0)) + (long long)(M - nsplit) * (1 + accumulate);
-    else out_ch = (long long)M * ((out0.p ? 1 : 0) + (s0.hi ? 1 : 0) + (aux0.p ? 1 : 0) + (saux.hi ? 1 : 0));
+    if (epi == EPI_GATE) out_ch = (long long)(M / 2) * ((op.out0.p ? 1 : 0) + (op.out1.p ? 2 : 0) + (op.s0.hi ? 1 : 0));
+    else if (epi == EPI_DGATE) out_ch = (long long)M * 2 /* tanh, sigmoid in */ + 2LL * M * ((op.s0.hi ? 1 : 0) + (op.out0.p ? 1 : 0));
+    else if (epi == EPI_RESSKIP) out_ch = (long long)op.nsplit * (1 + (op.out0.p ? 1 : 0) + (op.s0.hi ? 1 : 0)) + (long long)(M - op.nsplit) * (1 + op.accumulate);
+    else out_ch = (long long)M * ((op.out0.p ? 1 : 0) + (op.s0.hi ? 1 : 0) + (op.aux0.p ? 1 : 0) + (op.saux.hi ? 1 : 0));
     const long long alg_bytes = 4 * cols * (in_ch + out_ch) + 4LL * M * Ksum;
-    if (cx.cap && cx.prec != 2) { cx.cap->ok = false; return; }
-    if (cx.probe) *cx.probe = 0;
-    TimerScope ts((cx.rec || cx.cap || cx.probe) ? -1000 : WG_K_CONV_STORE + epi, cx.st, M, Ksum, cols, alg_bytes);      // (nothing is launched while recording)
-    if (cx.prec) {
-        ConvGemm16Args a16;
-        int K = 0, nc = 0;
-        for (int s = 0; s < nseg; ++s) { K += segs[s].nch; nc += (segs[s].nch + WG16_BK - 1) / WG16_BK; }
-        a16.img = mat_img(A, K, lda);
-        a16.img_stride = (size_t)nc * lda * WG16_BK;
-        a16.c = a;
-        if (cx.prec == 2) {
-            ConvGemm16sArgs as;
-            as.ntx = as.nty = as.ntz = 0; as.xcd_items = 0; as.tap_il = 0; as.tap_chunks = 0;
-#if !defined(WG_OPT_NO_TAP_IL)
-            {   // leading segments that are taps of one plane: walked interleaved (ConvGemm16sArgs::tap_il)
-                int nt = 1;
-                while (nt < nseg && segs[nt].s == segs[0].s && segs[nt].nch == segs[0].nch && segs[nt].sCp == segs[0].sCp &&
-                       segs[nt].sch0 == segs[0].sch0 && segs[nt].per_item == segs[0].per_item) ++nt;
-                if (nt >= 2 && segs[0].s && segs[0].nch % WG16_BK == 0) { as.tap_il = nt; as.tap_chunks = segs[0].nch / WG16_BK; }
-            }
-#endif
-            as.img = a16.img; as.img_stride = a16.img_stride; as.c = a; as.s0 = s0; as.saux = saux;
-            as.eff = nullptr; as.part = nullptr; as.prow = cx.gate_prow;
-            if (epi == EPI_GATE && cx.gate_part && (size_t)(M / 64) * 1024 <= WGG_EFF_BYTES) { as.eff = cx.gate_eff; as.part = cx.gate_part; }
-            for (int s = 0; s < nseg; ++s) {
-                as.sseg[s].hi = (const unsigned short *)segs[s].s;
-                as.sseg[s].lo_off = (size_t)(segs[s].per_item ? g.B / g.rows : g.B) * segs[s].sCp * g.P;
-                as.sseg[s].Cp = segs[s].sCp; as.sseg[s].ch0 = segs[s].sch0;
-                as.sseg[s].row_off = segs[s].row_off; as.sseg[s].per_item = segs[s].per_item;
-                if (!segs[s].s && !cx.err) cx.err = WG_EINVAL;
-                if ((segs[s].row_off || segs[s].per_item) && g.rows <= 0 && !cx.err) cx.err = WG_EINVAL;
-            }
-#if defined(WG_OPT_DMA)                           // LDS-DMA loader ring (6 waves per workgroup)
-            switch (epi) {
-            case EPI_STORE: WG_LAUNCH(cx, convgemm16d_kernel<EPI_STORE>, grid, dim3(384), 0, as); break;
-            case EPI_GATE: WG_LAUNCH(cx, convgemm16d_kernel<EPI_GATE>, grid, dim3(384), 0, as); break;
-            case EPI_RESSKIP: WG_LAUNCH(cx, convgemm16d_kernel<EPI_RESSKIP>, grid, dim3(384), 0, as); break;
-            case EPI_DGATE: WG_LAUNCH(cx, convgemm16d_kernel<EPI_DGATE>, grid, dim3(384), 0, as); break;
-            }
-            return;
-#elif !defined(WG_OPT_NO_WSPEC)                   // default: loader waves + compute waves (8 waves per workgroup)
-            // persistent launch: one workgroup per resident slot (two per CU), each walking its share of the tile grid -- see the
-            // kernel; the gate backward stays at one workgroup per tile.  -DWG_OPT_NO_PERSIST: one workgroup per tile everywhere.
-            const int cus = device_cus();
-            bool small = grid.x * grid.y * grid.z < 384;         // fewer 128x128 tiles than 3/4 of the workgroup slots: 128x64 tiles
-#if defined(WG_OPT_NI1_MASK)                      // experiment: 128 x 64 tiles (twice the tiles: a fuller last round) for a class of launches
-            if ((WG_OPT_NI1_MASK & 1) && epi == EPI_STORE && Ksum <= 256) small = true;
-            if ((WG_OPT_NI1_MASK & 2) && epi == EPI_DGATE) small = true;
-            if ((WG_OPT_NI1_MASK & 4) && epi == EPI_STORE && Ksum >= 1024 && Ksum < 2048) small = true;
-            if ((WG_OPT_NI1_MASK & 8) && epi == EPI_STORE && Ksum >= 2048) small = true;
-#endif
-            as.ntx = small ? (int)grid.x * 2 : (int)grid.x; as.nty = (int)grid.y; as.ntz = (int)grid.z;
-            const int ntiles = as.ntx * as.nty * as.ntz;
-            int slots = epi == EPI_DGATE ? ntiles : 2 * cus;
-#if defined(WG_OPT_NO_PERSIST)
-            slots = ntiles;
-#endif
-            const dim3 gp = epi == EPI_DGATE ? dim3(as.ntx, as.nty, as.ntz) : dim3(std::min(ntiles, slots));
-            // plane rows dealt to XCDs (ConvGemm16sArgs::xcd_items): full persistent grids whose plane rows divide by the 8 XCDs
-            const bool xcd_rows = epi != EPI_DGATE && as.ntz % 8 == 0 && g.rows == 0
-#if defined(WG_OPT_NO_XCD_ROWS)
-                                  && false
-#endif
-                ;
-            if (xcd_rows && ntiles >= slots && slots % 8 == 0) as.xcd_items = as.ntz / 8;
-#if !defined(WG_OPT_NO_XCD_COLS)
-            // XCD columns (ConvGemm16sArgs::xcd_items < 0): full persistent grids whose plane rows do NOT divide by the 8 XCDs
-            // (measured, WSRGlow at batch 12: the conditioning gradient -- 29 row tiles -- 516.9 -> 478.6 us; launches with few row tiles do not
-            // gain -- the gate conv, 4 row tiles: 107.6 -> 109.3 us -- so the order is used from 8 row tiles on)
-            else if (epi != EPI_DGATE && g.rows == 0 && !cx.row_sel1 && ntiles >= slots && slots % 8 == 0 && as.ntx * as.ntz >= 8 && as.nty >= 8) as.xcd_items = -1;
-#endif
-            if (cx.cap) {                                     // describe, do not launch: the 256 x 128-tile form with S-plane-only epilogues
-                const bool sg = epi == EPI_GATE && as.s0.hi && !a.out0.p && WG_TS_INTERLEAVED;
-                const bool se = epi == EPI_STORE && as.s0.hi && !a.out0.p && !a.aux0.p;
-                cx.cap->ok = !small && rup(mrows, WG_TILE) % 256 == 0 && (sg || se) && !cx.row_sel1 && g.rows == 0 && !cx.rec;
-                if (cx.cap->ok) {
-                    as.nty = (int)grid.y / 2;
-                    as.xcd_items = as.ntz % 8 == 0 ? as.ntz / 8 : 0;
-                    cx.cap->as = as;
-                }
-                return;
-            }
-#if !defined(WG_OPT_MFMA32)                       // default: the 16x16x32 form of the same kernel (wg_gemm16q.h)
-#if !defined(WG_OPT_NO_HTILE)
-            // at most half as many 128 x 64 tiles as CUs (one utterance being synthesised, WaveFlow's row-by-row inverse): such a launch
-            // is as long as its slowest CU needs to take in its operands -- 64 x 64 tiles, twice the workgroups (wg_gemm16h.h)
-            // (measured and not adopted: also where the 128 x 64 tiles are 1 - 1.5 per CU -- WSRGlow's gate conv, 384 such tiles --
-            // three 64 x 64 tiles on every CU instead: 52.9 against 50.5 ms per WSRGlow step)
-            if (small && 2 * ntiles <= cus && epi != EPI_DGATE) {
-                as.nty = 2 * (int)grid.y;
-                const dim3 gh(as.ntx * as.nty * as.ntz);
-                if (cx.rec) {                                 // (the stage interpreter runs convgemm16h_body on this argument block)
-                    cx.rec->add(epi == EPI_STORE ? WGS_CONV_STORE : epi == EPI_GATE ? WGS_CONV_GATE : WGS_CONV_RESSKIP, (int)gh.x).u.conv = as;
-                    return;
-                }
-                // (measured slower in round 5: the same tiles with the operands by LDS-DMA into a ring of eight chunk buffers, seven chunks in
-                // flight, four waves that multiply and issue -- git show 4c099e9:tools/experiments/wg_gemm16m.h: 2.70 against 2.46-2.52 ms per 0.7 s utterance,
-                // WaveFlow's row-by-row synthesis 96.6 against 86.7 ms: a CU's intake rate, not the depth of its prefetch, bounds these launches)
-                // (2 or 4 k-steps per chunk and barrier measured slower: git show 4c099e9:tools/experiments/wg_gemm16hk.h)
-                switch (epi) {
-                case EPI_STORE: WG_LAUNCH(cx, convgemm16h_kernel<EPI_STORE>, gh, dim3(512), 0, as); break;
-                case EPI_GATE: WG_LAUNCH(cx, convgemm16h_kernel<EPI_GATE>, gh, dim3(512), 0, as); break;
-                case EPI_RESSKIP: WG_LAUNCH(cx, convgemm16h_kernel<EPI_RESSKIP>, gh, dim3(512), 0, as); break;
-                }
-                return;
-            }
-#endif
-            // S-plane-only stores (no fp32 output, no fp32 accumulate-into plane): the instantiation with the hand-issued epilogue (EPI_STORE_SO)
-            const bool so_epi = epi == EPI_STORE && as.s0.hi && !a.out0.p && !a.aux0.p
-#if defined(WG_OPT_NO_EPI_BATCH)
-                                && false
-#endif
-                ;
-            const bool so_gate = epi == EPI_GATE && as.s0.hi && !a.out0.p && WG_TS_INTERLEAVED
-#if defined(WG_OPT_NO_EPI_BATCH)
-                                 && false
-#endif
-                ;
-            const bool so_dgate = epi == EPI_DGATE && as.s0.hi && !a.out0.p && WG_TS_INTERLEAVED
-#if defined(WG_OPT_NO_EPI_BATCH)
-                                  && false
-#endif
-                ;
-            const bool fo_epi = epi == EPI_STORE && !as.s0.hi && a.out0.p && !as.saux.hi
-#if defined(WG_OPT_NO_EPI_BATCH)
-                                && false
-#endif
-                ;
-#if !defined(WG_OPT_NO_G192)
-            // 256 x 192 tiles over flattened columns, eight multiplying waves fed by LDS-DMA (wg_gemm16g.h): the S-plane-only gate conv and
-            // store / data-gradient / skip products whose tiles deal out evenly over the CUs (env WG_G192=0 restores the 256 x 128 / 128 x 128 forms)
-            // (products of fewer than 16 chunks -- the residual conv, K = 256: 36.6 against 35.3 us -- stay on the older kernel: a tile that
-            // short is mostly this kernel's longer prologue; S-plane arrays and weight images beyond 4 GB: its 32-bit offsets)
-            // a gate conv whose tiles cannot fill the chip, cut along K (WSRGlow: 64 tiles, 139 chunks -> 4 parts of 35 on 256 workgroups) --
-            // the parts go to the workspace's slab (wn_ws_layout sizes it for this in every mode, so a plain forward and a training step's
-            // forward sum K in the same order; env WG_G192_SPLITK=0: off).  Never a gate conv asked for its partial rows of `out`: the cut
-            // writes none, and the uncut kernels with the rows are the faster pass (WaveGlow-256 at 6 x 16 000, layers 1-7 of every WN
-            // cut and the end conv over the gate planes: 23.9 against 21.7 ms per step)
-            if (g192_on() && so_gate && !as.part && g.rows == 0 && !cx.row_sel1 && !cx.rec && M % WGG_BM == 0 && g.H >= 64 && cus % 8 == 0 && cx.gslab &&
-                g192_fits(as, a16.img_stride, nseg)) {
-                const int nct = (g.B * g.Tt + WGG_BN - 1) / WGG_BN, nrb = M / WGG_BM;
-                int nt, S;
-                gate_split_plan(g.B * g.Tt, M, nc, cus, nt, S);
-                const size_t need = (size_t)S * nt * 8 * 24 * 256;
-                if (env_sw().g192_splitk && S && need <= cx.gslab_floats) {
-                    if (cx.probe) { *cx.probe = 0; return; }  // (the cut gate conv does not write the partial rows)
-                    ConvGemm16sArgs ap = as;
-                    ap.eff = nullptr; ap.part = nullptr;
-                    ap.ntx = nct; ap.nty = nrb; ap.ntz = S; ap.xcd_items = 2;
-                    ap.c.out0.p = cx.gslab;
-                    WG_LAUNCH(cx, convgemm16g_kernel<WGG_EPI_PART>, dim3(cus), dim3(512), 0, ap);
-                    ap.c.out0 = a.out0;
-                    WG_LAUNCH(cx, gate_finish16g_kernel, dim3(nt * 6), dim3(512), 0, ap, (const float *)cx.gslab, S);
-                    g_gate_split_launches.fetch_add(1, std::memory_order_relaxed);
-                    g_last_launch = "convgemm16g_kernel<WGG_EPI_PART> + gate_finish16g_kernel";      // (one timed class entry covers both)
-                    return;
-                }
-            }
-            const bool fo_g = fo_epi && !a.aux0.p;               // (the skip sum: fp32 plane out, nothing to accumulate into)
-            if (g192_on() && !small && (so_gate || so_epi || fo_g) && g.rows == 0 && !cx.row_sel1 && !cx.rec && M % WGG_BM == 0 && g.H >= 64 && cus % 8 == 0 &&
-                nc >= 16 && nc <= WGG_MAXCHUNKS && g192_fits(as, a16.img_stride, nseg)) {
-                const int nct = (g.B * g.Tt + WGG_BN - 1) / WGG_BN, nrb = M / WGG_BM, nt = nct * nrb;
-                const int rounds = (nt + cus - 1) / cus;
-                if (nt >= cus && (double)(rounds * cus - nt) <= 0.1 * rounds * cus) {
-                    as.ntx = nct; as.nty = nrb; as.ntz = 1; as.xcd_items = 0;
-                    if (env_sw().g192_own) as.xcd_items = 1;                                   // experiment: column ownership
-                    if (as.prow != 8) as.part = nullptr;      // (this kernel's epilogue writes 8-float rows)
-                    if (cx.probe) { *cx.probe = (so_gate && as.part) ? 1 : 0; return; }
-                    if (so_gate && as.part) { ++cx.part_written; g_gate_part_launches.fetch_add(1, std::memory_order_relaxed); }
-                    if (so_gate) WG_LAUNCH(cx, convgemm16g_kernel<EPI_GATE_SO>, dim3(cus), dim3(512), 0, as);
-                    else if (fo_g) WG_LAUNCH(cx, convgemm16g_kernel<EPI_STORE_FO>, dim3(cus), dim3(512), 0, as);
-                    else WG_LAUNCH(cx, convgemm16g_kernel<EPI_STORE_SO>, dim3(cus), dim3(512), 0, as);
-                    return;
-                }
-            }
-#endif
-#if !defined(WG_OPT_NO_M64)
-            // products with at most 64 rows on 64 x 128 tiles (convgemm16q_kernel<.., M64>): WaveFlow's 64-channel WN2D -- on 128-row tiles
-            // half of every MFMA multiplied padding (the data-gradient conv: 181 TF against 314 for the full-height gate conv)
-            if (!small && M <= 64 && epi != EPI_GATE && epi != EPI_RESSKIP) {
-                if (fo_epi) { WG_LAUNCH(cx, (convgemm16q_kernel<EPI_STORE_FO, 2, 1, true>), gp, dim3(512), 0, as); return; }
-                if (so_dgate) { WG_LAUNCH(cx, (convgemm16q_kernel<EPI_DGATE_SO, 2, 1, true>), gp, dim3(512), 0, as); return; }
-                if (so_epi) { WG_LAUNCH(cx, (convgemm16q_kernel<EPI_STORE_SO, 2, 1, true>), gp, dim3(512), 0, as); return; }
-                if (epi == EPI_STORE) { WG_LAUNCH(cx, (convgemm16q_kernel<EPI_STORE, 2, 1, true>), gp, dim3(512), 0, as); return; }
-                if (epi == EPI_DGATE) { WG_LAUNCH(cx, (convgemm16q_kernel<EPI_DGATE, 2, 1, true>), gp, dim3(512), 0, as); return; }
-            }
-#endif
-            if (small) {
-                if (fo_epi) { WG_LAUNCH(cx, (convgemm16q_kernel<EPI_STORE_FO, 1>), gp, dim3(512), 0, as); return; }
-                if (so_dgate) { WG_LAUNCH(cx, (convgemm16q_kernel<EPI_DGATE_SO, 1>), gp, dim3(512), 0, as); return; }
-                if (so_gate) { if (cx.probe) { *cx.probe = as.part ? 1 : 0; return; } if (as.part) { ++cx.part_written; g_gate_part_launches.fetch_add(1, std::memory_order_relaxed); } WG_LAUNCH(cx, (convgemm16q_kernel<EPI_GATE_SO, 1>), gp, dim3(512), 0, as); return; }
-                if (so_epi) { WG_LAUNCH(cx, (convgemm16q_kernel<EPI_STORE_SO, 1>), gp, dim3(512), 0, as); return; }
-                switch (epi) {
-                case EPI_STORE: WG_LAUNCH(cx, (convgemm16q_kernel<EPI_STORE, 1>), gp, dim3(512), 0, as); break;
-                case EPI_GATE: WG_LAUNCH(cx, (convgemm16q_kernel<EPI_GATE, 1>), gp, dim3(512), 0, as); break;
-                case EPI_RESSKIP: WG_LAUNCH(cx, (convgemm16q_kernel<EPI_RESSKIP, 1>), gp, dim3(512), 0, as); break;
-                case EPI_DGATE: WG_LAUNCH(cx, (convgemm16q_kernel<EPI_DGATE, 1>), gp, dim3(512), 0, as); break;
-                }
-                return;
-            }
-#if !defined(WG_OPT_NO_CG2)
-            // products with ONE 128-row tile (WaveFlow's gate conv, M = 2 Cd = 128) on 128 x 256 tiles: one 16-wave workgroup per CU whose two
-            // compute groups share the A image of every chunk (convgemm16q_kernel<.., CG2>) -- 25 % less L2 -> LDS traffic for a launch
-            // that sits at the per-CU intake limit
-            if (epi == EPI_GATE && (int)grid.y == 1 && g.Tt % 256 == 0 && cus % 8 == 0) {
-                as.ntx = (int)grid.x / 2;
-                const int nt2 = as.ntx * as.nty * as.ntz;
-                if (nt2 >= cus) {
-                    as.xcd_items = 0;
-                    const dim3 gc(std::min(nt2, cus));
-                    if (so_gate) { if (cx.probe) { *cx.probe = as.part ? 1 : 0; return; } if (as.part) { ++cx.part_written; g_gate_part_launches.fetch_add(1, std::memory_order_relaxed); } WG_LAUNCH(cx, (convgemm16q_kernel<EPI_GATE_SO, 2, 2, false, true>), gc, dim3(1024), 0, as); return; }
-                    WG_LAUNCH(cx, (convgemm16q_kernel<EPI_GATE, 2, 2, false, true>), gc, dim3(1024), 0, as);
-                    return;
-                }
-                as.ntx = (int)grid.x;
-            }
-#endif
-#if !defined(WG_OPT_NO_MG2)
-            // 256 x 128 tiles, one 16-wave workgroup per CU (the compute groups share every chunk's B image: 25 % less L2 -> LDS
-            // traffic, no slower co-resident workgroup left to finish alone): gate conv 125.7 -> 118.6 us.  Only where the tiles deal out
-            // evenly over the CUs: at 1.5 tiles per CU (the 256-row products of the training shape: 384 such tiles) the half-empty second
-            // round costs more than the sharing saves (measured: step 81.8 -> 83.0 ms with every eligible launch on this path).
-            // (1.69 such tiles per CU -- the gate conv of a 10 s utterance -- still gain 4 %: 20.2 -> 21.0 MHz; 1.5 per CU lose)
-            const int rounds = (ntiles / 2 + cus - 1) / cus;
-            const bool mg2_ok = ntiles / 2 >= cus && (double)(rounds * cus - ntiles / 2) <= 0.17 * rounds * cus;
-            if (epi != EPI_DGATE && rup(mrows, WG_TILE) % 256 == 0 && mg2_ok) {
-                as.nty = (int)grid.y / 2;
-                const dim3 g2(std::min(ntiles / 2, cus));
-                if (cus % 8) as.xcd_items = 0;                // (mg2_ok: at least one tile per CU)
-                if (so_epi) { WG_LAUNCH(cx, (convgemm16q_kernel<EPI_STORE_SO, 2, 2>), g2, dim3(1024), 0, as); return; }
-                if (so_gate) { if (cx.probe) { *cx.probe = as.part ? 1 : 0; return; } if (as.part) { ++cx.part_written; g_gate_part_launches.fetch_add(1, std::memory_order_relaxed); } WG_LAUNCH(cx, (convgemm16q_kernel<EPI_GATE_SO, 2, 2>), g2, dim3(1024), 0, as); return; }
-                if (fo_epi) { WG_LAUNCH(cx, (convgemm16q_kernel<EPI_STORE_FO, 2, 2>), g2, dim3(1024), 0, as); return; }
-                switch (epi) {
-                case EPI_STORE: WG_LAUNCH(cx, (convgemm16q_kernel<EPI_STORE, 2, 2>), g2, dim3(1024), 0, as); break;
-                case EPI_GATE: WG_LAUNCH(cx, (convgemm16q_kernel<EPI_GATE, 2, 2>), g2, dim3(1024), 0, as); break;
-                case EPI_RESSKIP: WG_LAUNCH(cx, (convgemm16q_kernel<EPI_RESSKIP, 2, 2>), g2, dim3(1024), 0, as); break;
-                }
-                return;
-            }
-#endif
-            if (so_epi) { WG_LAUNCH(cx, (convgemm16q_kernel<EPI_STORE_SO, 2>), gp, dim3(512), 0, as); return; }
-            if (so_gate) { if (cx.probe) { *cx.probe = as.part ? 1 : 0; return; } if (as.part) { ++cx.part_written; g_gate_part_launches.fetch_add(1, std::memory_order_relaxed); } WG_LAUNCH(cx, (convgemm16q_kernel<EPI_GATE_SO, 2>), gp, dim3(512), 0, as); return; }
-            if (so_dgate) { WG_LAUNCH(cx, (convgemm16q_kernel<EPI_DGATE_SO, 2>), gp, dim3(512), 0, as); return; }
-            if (fo_epi) { WG_LAUNCH(cx, (convgemm16q_kernel<EPI_STORE_FO, 2>), gp, dim3(512), 0, as); return; }
-            switch (epi) {
-            case EPI_STORE: WG_LAUNCH(cx, (convgemm16q_kernel<EPI_STORE, 2>), gp, dim3(512), 0, as); break;
-            case EPI_GATE: WG_LAUNCH(cx, (convgemm16q_kernel<EPI_GATE, 2>), gp, dim3(512), 0, as); break;
-            case EPI_RESSKIP: WG_LAUNCH(cx, (convgemm16q_kernel<EPI_RESSKIP, 2>), gp, dim3(512), 0, as); break;
-            case EPI_DGATE: WG_LAUNCH(cx, (convgemm16q_kernel<EPI_DGATE, 2>), gp, dim3(512), 0, as); break;
-            }
-            return;
-#else                                             // A/B build -DWG_OPT_MFMA32: the 32x32x16 kernel (git show 4c099e9:tools/experiments/wg_gemm16_superseded.h)
-            if (small) {
-                switch (epi) {
-                case EPI_STORE: WG_LAUNCH(cx, (convgemm16w_kernel<EPI_STORE, 1>), gp, dim3(512), 0, as); break;
-                case EPI_GATE: WG_LAUNCH(cx, (convgemm16w_kernel<EPI_GATE, 1>), gp, dim3(512), 0, as); break;
-                case EPI_RESSKIP: WG_LAUNCH(cx, (convgemm16w_kernel<EPI_RESSKIP, 1>), gp, dim3(512), 0, as); break;
-                case EPI_DGATE: WG_LAUNCH(cx, (convgemm16w_kernel<EPI_DGATE, 1>), gp, dim3(512), 0, as); break;
-                }
-                return;
-            }
-            switch (epi) {
-            case EPI_STORE: WG_LAUNCH(cx, (convgemm16w_kernel<EPI_STORE, 2>), gp, dim3(512), 0, as); break;
-            case EPI_GATE: WG_LAUNCH(cx, (convgemm16w_kernel<EPI_GATE, 2>), gp, dim3(512), 0, as); break;
-            case EPI_RESSKIP: WG_LAUNCH(cx, (convgemm16w_kernel<EPI_RESSKIP, 2>), gp, dim3(512), 0, as); break;
-            case EPI_DGATE: WG_LAUNCH(cx, (convgemm16w_kernel<EPI_DGATE, 2>), gp, dim3(512), 0, as); break;
-            }
-            return;
-#endif
-#else                                             // A/B build: the symmetric software-pipelined kernel
-            switch (epi) {
-            case EPI_STORE: WG_LAUNCH(cx, convgemm16p_kernel<EPI_STORE>, grid, block, 0, as); break;
-            case EPI_GATE: WG_LAUNCH(cx, convgemm16p_kernel<EPI_GATE>, grid, block, 0, as); break;
-            case EPI_RESSKIP: WG_LAUNCH(cx, convgemm16p_kernel<EPI_RESSKIP>, grid, block, 0, as); break;
-            case EPI_DGATE: WG_LAUNCH(cx, convgemm16p_kernel<EPI_DGATE>, grid, block, 0, as); break;
-            }
-            return;
-#endif
-        }
-        const bool big = (rup(mrows, WG_TILE) % 256) == 0;      // 256-row tiles when M allows it
-        if (big) {
-            dim3 grid4(g.Tt / WG_TILE, rup(mrows, WG_TILE) / 256, g.B), block4(512);
-            switch (epi) {
-            case EPI_STORE: WG_LAUNCH(cx, (convgemm16_kernel<EPI_STORE, 4>), grid4, block4, 0, a16); break;
-            case EPI_GATE: WG_LAUNCH(cx, (convgemm16_kernel<EPI_GATE, 4>), grid4, block4, 0, a16); break;
-            case EPI_RESSKIP: WG_LAUNCH(cx, (convgemm16_kernel<EPI_RESSKIP, 4>), grid4, block4, 0, a16); break;
-            case EPI_DGATE: WG_LAUNCH(cx, (convgemm16_kernel<EPI_DGATE, 4>), grid4, block4, 0, a16); break;
-            }
-        } else {
-            switch (epi) {
-            case EPI_STORE: WG_LAUNCH(cx, (convgemm16_kernel<EPI_STORE, 2>), grid, block, 0, a16); break;
-            case EPI_GATE: WG_LAUNCH(cx, (convgemm16_kernel<EPI_GATE, 2>), grid, block, 0, a16); break;
-            case EPI_RESSKIP: WG_LAUNCH(cx, (convgemm16_kernel<EPI_RESSKIP, 2>), grid, block, 0, a16); break;
-            case EPI_DGATE: WG_LAUNCH(cx, (convgemm16_kernel<EPI_DGATE, 2>), grid, block, 0, a16); break;
-            }
-        }
+    TimerScope ts(WG_K_CONV_STORE + epi, cx.st, M, Ksum, cols, alg_bytes);
+    if (rt.part) { ++cx.part_written; g_gate_part_launches.fetch_add(1, std::memory_order_relaxed); }
+    ConvGemm16Args a16;
+    a16.img = as.img; a16.img_stride = as.img_stride; a16.c = as.c;
+    switch (ck(rt.kern, rt.epi)) {
+    case ck(CK_F32, EPI_STORE): WG_LAUNCH(cx, convgemm_kernel<EPI_STORE>, rt.grid, rt.block, 0, as.c); return;
+    case ck(CK_F32, EPI_GATE): WG_LAUNCH(cx, convgemm_kernel<EPI_GATE>, rt.grid, rt.block, 0, as.c); return;
+    case ck(CK_F32, EPI_RESSKIP): WG_LAUNCH(cx, convgemm_kernel<EPI_RESSKIP>, rt.grid, rt.block, 0, as.c); return;
+    case ck(CK_F32, EPI_DGATE): WG_LAUNCH(cx, convgemm_kernel<EPI_DGATE>, rt.grid, rt.block, 0, as.c); return;
+    case ck(CK_16, EPI_STORE): WG_LAUNCH(cx, (convgemm16_kernel<EPI_STORE, 2>), rt.grid, rt.block, 0, a16); return;
+    case ck(CK_16, EPI_GATE): WG_LAUNCH(cx, (convgemm16_kernel<EPI_GATE, 2>), rt.grid, rt.block, 0, a16); return;
+    case ck(CK_16, EPI_RESSKIP): WG_LAUNCH(cx, (convgemm16_kernel<EPI_RESSKIP, 2>), rt.grid, rt.block, 0, a16); return;
+    case ck(CK_16, EPI_DGATE): WG_LAUNCH(cx, (convgemm16_kernel<EPI_DGATE, 2>), rt.grid, rt.block, 0, a16); return;
+    case ck(CK_16_MT4, EPI_STORE): WG_LAUNCH(cx, (convgemm16_kernel<EPI_STORE, 4>), rt.grid, rt.block, 0, a16); return;
+    case ck(CK_16_MT4, EPI_GATE): WG_LAUNCH(cx, (convgemm16_kernel<EPI_GATE, 4>), rt.grid, rt.block, 0, a16); return;
+    case ck(CK_16_MT4, EPI_RESSKIP): WG_LAUNCH(cx, (convgemm16_kernel<EPI_RESSKIP, 4>), rt.grid, rt.block, 0, a16); return;
+    case ck(CK_16_MT4, EPI_DGATE): WG_LAUNCH(cx, (convgemm16_kernel<EPI_DGATE, 4>), rt.grid, rt.block, 0, a16); return;
+    case ck(CK_H, EPI_STORE): WG_LAUNCH(cx, convgemm16h_kernel<EPI_STORE>, rt.grid, rt.block, 0, as); return;
+    case ck(CK_H, EPI_GATE): WG_LAUNCH(cx, convgemm16h_kernel<EPI_GATE>, rt.grid, rt.block, 0, as); return;
+    case ck(CK_H, EPI_RESSKIP): WG_LAUNCH(cx, convgemm16h_kernel<EPI_RESSKIP>, rt.grid, rt.block, 0, as); return;
+    case ck(CK_G_SPLIT, WGG_EPI_PART): {
+        ConvGemm16sArgs ap = as;                      // the K parts go to the slab, the finishing launch sums them into the gate's planes
+        ap.c.out0.p = cx.gslab;
+        WG_LAUNCH(cx, convgemm16g_kernel<WGG_EPI_PART>, rt.grid, rt.block, 0, ap);
+        WG_LAUNCH(cx, gate_finish16g_kernel, dim3(rt.nt * 6), rt.block, 0, as, (const float *)cx.gslab, rt.S);
+        g_gate_split_launches.fetch_add(1, std::memory_order_relaxed);
+        g_last_launch = "convgemm16g_kernel<WGG_EPI_PART> + gate_finish16g_kernel";      // (one timed class entry covers both)
         return;
     }
-    switch (epi) {
-    case EPI_STORE: WG_LAUNCH(cx, convgemm_kernel<EPI_STORE>, grid, block, 0, a); break;
-    case EPI_GATE: WG_LAUNCH(cx, convgemm_kernel<EPI_GATE>, grid, block, 0, a); break;
-    case EPI_RESSKIP: WG_LAUNCH(cx, convgemm_kernel<EPI_RESSKIP>, grid, block, 0, a); break;
-    case EPI_DGATE: WG_LAUNCH(cx, convgemm_kernel<EPI_DGATE>, grid, block, 0, a); break;
+    case ck(CK_G, EPI_GATE_SO): WG_LAUNCH(cx, convgemm16g_kernel<EPI_GATE_SO>, rt.grid, rt.block, 0, as); return;
+    case ck(CK_G, EPI_STORE_FO): WG_LAUNCH(cx, convgemm16g_kernel<EPI_STORE_FO>, rt.grid, rt.block, 0, as); return;
+    case ck(CK_G, EPI_STORE_SO): WG_LAUNCH(cx, convgemm16g_kernel<EPI_STORE_SO>, rt.grid, rt.block, 0, as); return;
+    case ck(CK_Q_M64, EPI_STORE_FO): WG_LAUNCH(cx, (convgemm16q_kernel<EPI_STORE_FO, 2, 1, true>), rt.grid, rt.block, 0, as); return;
+    case ck(CK_Q_M64, EPI_DGATE_SO): WG_LAUNCH(cx, (convgemm16q_kernel<EPI_DGATE_SO, 2, 1, true>), rt.grid, rt.block, 0, as); return;
+    case ck(CK_Q_M64, EPI_STORE_SO): WG_LAUNCH(cx, (convgemm16q_kernel<EPI_STORE_SO, 2, 1, true>), rt.grid, rt.block, 0, as); return;
+    case ck(CK_Q_M64, EPI_STORE): WG_LAUNCH(cx, (convgemm16q_kernel<EPI_STORE, 2, 1, true>), rt.grid, rt.block, 0, as); return;
+    case ck(CK_Q_M64, EPI_DGATE): WG_LAUNCH(cx, (convgemm16q_kernel<EPI_DGATE, 2, 1, true>), rt.grid, rt.block, 0, as); return;
+    case ck(CK_Q1, EPI_STORE_FO): WG_LAUNCH(cx, (convgemm16q_kernel<EPI_STORE_FO, 1>), rt.grid, rt.block, 0, as); return;
+    case ck(CK_Q1, EPI_DGATE_SO): WG_LAUNCH(cx, (convgemm16q_kernel<EPI_DGATE_SO, 1>), rt.grid, rt.block, 0, as); return;
+    case ck(CK_Q1, EPI_GATE_SO): WG_LAUNCH(cx, (convgemm16q_kernel<EPI_GATE_SO, 1>), rt.grid, rt.block, 0, as); return;
+    case ck(CK_Q1, EPI_STORE_SO): WG_LAUNCH(cx, (convgemm16q_kernel<EPI_STORE_SO, 1>), rt.grid, rt.block, 0, as); return;
+    case ck(CK_Q1, EPI_STORE): WG_LAUNCH(cx, (convgemm16q_kernel<EPI_STORE, 1>), rt.grid, rt.block, 0, as); return;
+    case ck(CK_Q1, EPI_GATE): WG_LAUNCH(cx, (convgemm16q_kernel<EPI_GATE, 1>), rt.grid, rt.block, 0, as); return;
+    case ck(CK_Q1, EPI_RESSKIP): WG_LAUNCH(cx, (convgemm16q_kernel<EPI_RESSKIP, 1>), rt.grid, rt.block, 0, as); return;
+    case ck(CK_Q1, EPI_DGATE): WG_LAUNCH(cx, (convgemm16q_kernel<EPI_DGATE, 1>), rt.grid, rt.block, 0, as); return;
+    case ck(CK_Q_CG2, EPI_GATE_SO): WG_LAUNCH(cx, (convgemm16q_kernel<EPI_GATE_SO, 2, 2, false, true>), rt.grid, rt.block, 0, as); return;
+    case ck(CK_Q_CG2, EPI_GATE): WG_LAUNCH(cx, (convgemm16q_kernel<EPI_GATE, 2, 2, false, true>), rt.grid, rt.block, 0, as); return;
+    case ck(CK_Q_MG2, EPI_STORE_SO): WG_LAUNCH(cx, (convgemm16q_kernel<EPI_STORE_SO, 2, 2>), rt.grid, rt.block, 0, as); return;
+    case ck(CK_Q_MG2, EPI_GATE_SO): WG_LAUNCH(cx, (convgemm16q_kernel<EPI_GATE_SO, 2, 2>), rt.grid, rt.block, 0, as); return;
+    case ck(CK_Q_MG2, EPI_STORE_FO): WG_LAUNCH(cx, (convgemm16q_kernel<EPI_STORE_FO, 2, 2>), rt.grid, rt.block, 0, as); return;
+    case ck(CK_Q_MG2, EPI_STORE): WG_LAUNCH(cx, (convgemm16q_kernel<EPI_STORE, 2, 2>), rt.grid, rt.block, 0, as); return;
+    case ck(CK_Q_MG2, EPI_GATE): WG_LAUNCH(cx, (convgemm16q_kernel<EPI_GATE, 2, 2>), rt.grid, rt.block, 0, as); return;
+    case ck(CK_Q_MG2, EPI_RESSKIP): WG_LAUNCH(cx, (convgemm16q_kernel<EPI_RESSKIP, 2, 2>), rt.grid, rt.block, 0, as); return;
+    case ck(CK_Q2, EPI_STORE_SO): WG_LAUNCH(cx, (convgemm16q_kernel<EPI_STORE_SO, 2>), rt.grid, rt.block, 0, as); return;
+    case ck(CK_Q2, EPI_GATE_SO): WG_LAUNCH(cx, (convgemm16q_kernel<EPI_GATE_SO, 2>), rt.grid, rt.block, 0, as); return;
+    case ck(CK_Q2, EPI_DGATE_SO): WG_LAUNCH(cx, (convgemm16q_kernel<EPI_DGATE_SO, 2>), rt.grid, rt.block, 0, as); return;
+    case ck(CK_Q2, EPI_STORE_FO): WG_LAUNCH(cx, (convgemm16q_kernel<EPI_STORE_FO, 2>), rt.grid, rt.block, 0, as); return;
+    case ck(CK_Q2, EPI_STORE): WG_LAUNCH(cx, (convgemm16q_kernel<EPI_STORE, 2>), rt.grid, rt.block, 0, as); return;
+    case ck(CK_Q2, EPI_GATE): WG_LAUNCH(cx, (convgemm16q_kernel<EPI_GATE, 2>), rt.grid, rt.block, 0, as); return;
+    case ck(CK_Q2, EPI_RESSKIP): WG_LAUNCH(cx, (convgemm16q_kernel<EPI_RESSKIP, 2>), rt.grid, rt.block, 0, as); return;
+    case ck(CK_Q2, EPI_DGATE): WG_LAUNCH(cx, (convgemm16q_kernel<EPI_DGATE, 2>), rt.grid, rt.block, 0, as); return;
     }
+    if (!cx.err) cx.err = WG_EUNSUPPORTED;            // (a route without an instantiation: nothing was launched)
+}
+
+void run_convgemm(Ctx &cx, const ConvOp &op) { launch_conv(cx, op, route_conv(cx, op)); }
+void run_convgemm(Ctx &cx, const Geo &g, const float *A, int lda, int M, const SegSpec *segs, int nseg, int epi,
+                  PRef out0, PRef out1, PRef out2, PRef aux0, PRef aux1, int nsplit, int accumulate, SRef s0 = snull(), SRef saux = snull())
+{
+    run_convgemm(cx, conv_op(g, A, lda, M, segs, nseg, epi, out0, out1, out2, aux0, aux1, nsplit, accumulate, s0, saux));
 }
 
 struct WSegSpec {
@@ -1861,12 +1853,16 @@ __global__ void ones_fill_kernel(float *f32, unsigned short *hi, size_t lo_off, 
         }
     }
 }
-SegSpec ones_seg(Ctx &cx, const WnRun &r, bool fill)
+SegSpec ones_seg(const Ctx &cx, const WnRun &r)
+{
+    SegSpec s = {r.ws + r.w.ones, 32, 0, 32, 0, cx.prec == 2 ? r.ws + r.w.onesS : nullptr, 32, 0};
+    return s;
+}
+SegSpec ones_fill(Ctx &cx, const WnRun &r)                  // (the plane of ones written, at the start of a pass)
 {
     float *f = r.ws + r.w.ones, *sp = cx.prec == 2 ? r.ws + r.w.onesS : nullptr;
-    if (fill) WG_LAUNCH(cx, ones_fill_kernel, dim3((r.g.P + 255) / 256, r.g.B), dim3(256), 0, f, (unsigned short *)sp, (size_t)r.g.B * 32 * r.g.P, r.g);
-    SegSpec s = {f, 32, 0, 32, 0, sp, 32, 0};
-    return s;
+    WG_LAUNCH(cx, ones_fill_kernel, dim3((r.g.P + 255) / 256, r.g.B), dim3(256), 0, f, (unsigned short *)sp, (size_t)r.g.B * 32 * r.g.P, r.g);
+    return ones_seg(cx, r);
 }
 
 // The thin products of WN's backward (wg_thin.h): precision 2, inside a FinQueue (the partials come from its arena).
@@ -1935,17 +1931,31 @@ bool run_convlayer(Ctx &cx, float *ws, size_t lsync, FA &&gate_call, FB &&wo_cal
     return true;
 #endif
 }
+// A product of a one-launch layer below as its 256 x 128-tile argument block (ntx x nty x ntz tiles of 256 rows, plane rows dealt to the
+// XCDs where they divide by 8): the gate conv or a store with an S-plane-only epilogue, on more 128 x 128 tiles than the small grids take,
+// over every plane row.  false: the product does not qualify.
+static bool layer_args(const Ctx &cx, const ConvOp &op, ConvGemm16sArgs &as)
+{
+    const bool sg = op.epi == EPI_GATE && op.s0.hi && !op.out0.p && WG_TS_INTERLEAVED;
+    const bool se = op.epi == EPI_STORE && op.s0.hi && !op.out0.p && !op.aux0.p;
+    if (cx.prec != 2 || cx.rec || cx.row_sel1 || op.g.rows != 0 || !(sg || se) || rup(op.M, WG_TILE) % 256) return false;
+    const ConvRoute rt = conv_args(cx, op);
+    if (rt.err || conv_small(op, rt.grid)) return false;
+    as = rt.as;
+    as.ntx = (int)rt.grid.x; as.nty = (int)rt.grid.y / 2; as.ntz = (int)rt.grid.z;
+    as.xcd_items = as.ntz % 8 == 0 ? as.ntz / 8 : 0;
+    return true;
+}
 // A layer's gate conv and residual product as ONE persistent launch (wg_layer16q.h) where the gate conv fills the chip with 256 x 128 tiles
-// dealt by XCD rows in at least two whole rounds (the training shapes).  Both launches are only DESCRIBED (Ctx::cap), checked, and issued as
-// convlayer16q_kernel; false = nothing was launched (the caller issues the two launches the ordinary way).
+// dealt by XCD rows in at least two whole rounds (the training shapes).  Both products are taken as argument blocks (layer_args), checked,
+// and issued as convlayer16q_kernel; false = nothing was launched (the caller issues the two launches the ordinary way).
 std::atomic<long long> g_layerq_launches{0};                  // diagnostics: launches of convlayer16q_kernel (wg_stat_layerq_launches)
-template <class FA, class FB>
-bool run_convlayer_big(Ctx &cx, float *ws, size_t lsync, FA &&gate_call, FB &&res_call)
+bool run_convlayer_big(Ctx &cx, float *ws, size_t lsync, const ConvOp &gate, const ConvOp &res)
 {
 #if defined(WG_OPT_NO_LAYERQ)
     return false;
 #else
-    if (cx.prec != 2 || cx.rec || cx.cap || cx.err) return false;
+    if (cx.prec != 2 || cx.rec || cx.err) return false;
     {
         // OPT-IN (WG_LAYER_FUSION_BIG=1).  Measured at the headline shape (gpurun_out/r04g_bigfuse.txt, r04h_bisect.txt):
         // parity identical, 166-169 us per layer against 117.7 + 34.8 = 152.5 us for the two launches (step 65.9 against 64.3 ms).  The R tiles
@@ -1953,15 +1963,9 @@ bool run_convlayer_big(Ctx &cx, float *ws, size_t lsync, FA &&gate_call, FB &&re
         // the epilogue, the poll), exactly as in the stand-alone residual launch -- and the G tiles run 8 % slower in the two-shape loop.
         if (!env_sw().layer_fusion_big) return false;
     }
-    BigCap cg, cr;
-    cg.ok = cr.ok = false;
-    cx.cap = &cg;
-    gate_call();
-    cx.cap = &cr;
-    res_call();
-    cx.cap = nullptr;
-    if (!cg.ok || !cr.ok || cx.err) return false;
-    const ConvGemm16sArgs &A = cg.as, &R = cr.as;
+    ConvLayer16qArgs la;
+    if (!layer_args(cx, gate, la.p[0]) || !layer_args(cx, res, la.p[1])) return false;
+    const ConvGemm16sArgs &A = la.p[0], &R = la.p[1];
     const int cus = device_cus();
     if (cus % 16 || A.nty != 2 || R.nty != 1 || A.ntx != R.ntx || A.ntz != R.ntz || A.xcd_items <= 0) return false;
     if (R.c.nseg != 1 || R.sseg[0].hi != A.s0.hi || R.c.seg[0].shift || !R.saux.hi || R.c.M > 256) return false;     // the residual's operand IS the gate
@@ -1969,8 +1973,6 @@ bool run_convlayer_big(Ctx &cx, float *ws, size_t lsync, FA &&gate_call, FB &&re
     if (xl % xslots || xl / xslots < 2) return false;        // whole rounds, at least two (an R tile needs an item between it and its own G tile)
     const int ncol = A.ntx * A.ntz;
     if ((size_t)ncol * WGL_SYNC_STRIDE > WGL_SYNC_WORDS) return false;
-    ConvLayer16qArgs la;
-    la.p[0] = A; la.p[1] = R;
     la.sync = reinterpret_cast<unsigned *>(ws + lsync);
     long long KA = 0, in_ch = 0;
     for (int q = 0; q < A.c.nseg; ++q) {
@@ -1991,28 +1993,19 @@ bool run_convlayer_big(Ctx &cx, float *ws, size_t lsync, FA &&gate_call, FB &&re
 }
 
 // The layer as ONE launch of convlayer16g_kernel (wg_gemm16g.h): a workgroup owns whole 192-column tiles, computes both 256-row gate tiles
-// for them and then, from its own stores, the residual product -- nothing crosses workgroups.  The two launches are described through
-// the same capture as above; returns false (nothing launched) when the shapes do not qualify.  env WG_LAYER_G=0 switches it off.
+// for them and then, from its own stores, the residual product -- nothing crosses workgroups.  The two products are taken as argument
+// blocks as above (layer_args); returns false (nothing launched) when the shapes do not qualify.  env WG_LAYER_G=0 switches it off.
 std::atomic<long long> g_layerg_launches{0};                  // diagnostics (wg_stat_layer_launches)
-template <class FA, class FB>
-bool run_convlayer_g(Ctx &cx, FA &&gate_call, FB &&res_call)
+bool run_convlayer_g(Ctx &cx, const ConvOp &gate, const ConvOp &res)
 {
 #if defined(WG_OPT_NO_G192) || defined(WG_OPT_NO_LAYERG)
     return false;
 #else
     // (WG_LAYER_FUSION_BIG=1 asks for the older one-launch layer instead)
     if (!env_sw().layer_g || env_sw().layer_fusion_big) return false;
-    if (!g192_on() || cx.prec != 2 || cx.rec || cx.cap || cx.err) return false;
-    BigCap cg, cr;
-    cg.ok = cr.ok = false;
-    cx.cap = &cg;
-    gate_call();
-    cx.cap = &cr;
-    res_call();
-    cx.cap = nullptr;
-    if (!cg.ok || !cr.ok || cx.err) return false;
+    if (!g192_on() || cx.prec != 2 || cx.rec || cx.err) return false;
     ConvLayer16gArgs la;
-    la.p[0] = cg.as; la.p[1] = cr.as;
+    if (!layer_args(cx, gate, la.p[0]) || !layer_args(cx, res, la.p[1])) return false;
     ConvGemm16sArgs &A = la.p[0], &R = la.p[1];
     const Geo &g = A.c.g;
     const int cus = device_cus();
@@ -2063,9 +2056,6 @@ void layer_sync_clear(Ctx &cx, float *ws, size_t lsync)
 }
 
 struct WnRun;
-// layer i's gate conv (model/waveglow.py:42-44): dilated taps of h_i (plane / S-plane `hin`) + the conditioning -> gate (tanh, sigmoid
-// kept where the pass saves them); keepg: every layer's gate has its own plane
-static void wn_gate_conv(Ctx &cx, const WnRun &r, int i, int hin, bool keepg);
 // The WN runs in the rank-2ic form of its skip path (lowrank_shape; wg_small.h weff_kernel): no skip sum, no dS.  One predicate for the
 // forward, the recompute pass and the backward of a shape, so that a kept flow and a recomputed one produce the same bits: the shapes
 // whose forward keeps every layer's gate anyway (the one-product skip sum's, fs below).
@@ -2077,11 +2067,11 @@ static bool lowrank_base(const Ctx &cx, const WnRun &r)
     return env_sw().lowrank && cx.prec == 2 && lowrank_shape(r.d) && (2 * r.d.ic <= 8 || env_sw().lowrank_all) && r.L.effT && !cx.rec &&
            !cx.row_sel1 && (g.rows == 0 || r.d.mode2d) && g.B * g.Tt >= WG_FUSED_SKIP_MIN_COLS;
 }
-// Do this WN's gate convs leave their share of `out` (ConvGemm16sArgs::part)?  Asked of run_convgemm itself (Ctx::probe: the launch is
-// described, routed, and not run), so that the answer cannot drift from the routing: 1 = the kernel that writes the partial rows.
-static bool gate_parts_on(Ctx &cx, const WnRun &r);
+// Do this WN's gate convs leave their share of `out` (ConvGemm16sArgs::part)?  Asked of the router (route_conv), so that the answer
+// cannot drift from the routing: true = the kernel of every layer's route writes the partial rows.
+static bool gate_parts_on(const Ctx &cx, const WnRun &r);
 // (WaveFlow's WN2D, mode2d: only together with the partial rows -- its coupling kernel has no form that reads the gate planes)
-static bool lowrank_on(Ctx &cx, const WnRun &r) { return lowrank_base(cx, r) && (!r.d.mode2d || gate_parts_on(cx, r)); }
+static bool lowrank_on(const Ctx &cx, const WnRun &r) { return lowrank_base(cx, r) && (!r.d.mode2d || gate_parts_on(cx, r)); }
 // where end_affine_kernel takes `out` from: 0 = W_end . S (the skip plane), 1 = sum_l Weff_l gate_l straight from the gate planes,
 // 2 = the partial rows the gate convs left
 static int affine_source(Ctx &cx, const WnRun &r, AffineArgs &a)
@@ -2130,7 +2120,9 @@ static bool start_fold_on(const Ctx &cx, const WnRun &r)
 {
     return env_sw().start_fold && cx.prec == 2 && start_fold_shape(r.d) && r.L.Acat0x && !cx.rec && !cx.row_sel1 && (r.g.rows == 0 || r.d.mode2d);
 }
-static void wn_gate_conv(Ctx &cx, const WnRun &r, int i, int hin, bool keepg)
+// layer i's gate conv (model/waveglow.py:42-44): dilated taps of h_i (plane / S-plane `hin`) + the conditioning -> gate (tanh, sigmoid
+// kept where the pass saves them); keepg: every layer's gate has its own plane; rows: its epilogue leaves the layer's partial rows of `out`
+static ConvOp wn_gate_op(const Ctx &cx, const WnRun &r, int i, int hin, bool keepg, bool rows)
 {
     const WnD &d = r.d;
     const Geo &g = r.g;
@@ -2153,45 +2145,40 @@ static void wn_gate_conv(Ctx &cx, const WnRun &r, int i, int hin, bool keepg)
     if (false)
 #endif
     sg[ns++] = {r.Y, d.auxp(), 0, d.auxp(), 0, r.YS, d.auxp(), 0, 0, d.mode2d};
-    if (nb) sg[ns++] = ones_seg(cx, r, false);               // (wn_forward filled the plane of ones at the start of the pass)
-    run_convgemm(cx, g, r.pk + (fold ? r.L.Acat0x : r.L.Acat[i]), r.L.ld_Acat, 2 * d.Cd, sg, ns, EPI_GATE, sp ? pnull() : pref(gate, d.Cd),
-                 (r.save && !tw_from_gate(cx)) ? pref(ws + r.w.tw[i], d.Cd) : pnull(), r.save ? pref(ws + r.w.sf[i], d.Cd) : pnull(),
-                 pnull(), pnull(), 0, 0, sp ? sref(g, gateS, d.Cd) : snull());             // waveglow.py:42-44
+    if (nb) sg[ns++] = ones_seg(cx, r);                      // (wn_forward filled the plane of ones at the start of the pass)
+    ConvOp op = conv_op(g, r.pk + (fold ? r.L.Acat0x : r.L.Acat[i]), r.L.ld_Acat, 2 * d.Cd, sg, ns, EPI_GATE, sp ? pnull() : pref(gate, d.Cd),
+                        (r.save && !tw_from_gate(cx)) ? pref(ws + r.w.tw[i], d.Cd) : pnull(), r.save ? pref(ws + r.w.sf[i], d.Cd) : pnull(),
+                        pnull(), pnull(), 0, 0, sp ? sref(g, gateS, d.Cd) : snull());             // waveglow.py:42-44
+    if (rows) {
+        op.eff = r.pk + r.L.effA + (size_t)i * (d.Cd / 32) * 256;
+        op.part = ws + r.w.gpart + (size_t)i * r.w.gpart_step;
+        op.prow = gate_part_prow(d);
+    }
+    return op;
 }
 // the weight-gradient slab of a training workspace is idle while a WN runs forward (wn_backward's queue is flushed when it returns): scratch
-// for a split gate conv's parts.  `asked_outside`: the routing probe asks what a FORWARD pass of this WN does from wherever the answer is
-// needed -- behind wn_forward (the end conv's source), inside wn_backward (its queue owns the slab then) -- and must see what that pass saw:
-// without it a WN whose gate convs are cut along K (no partial rows) was told, after the pass, that they had been written.
+// for a split gate conv's parts -- not while wn_backward's queue owns the slab (Ctx::fq)
 struct GslabScope {
     Ctx &c;
     float *p0;
     size_t n0;
-    GslabScope(Ctx &cx_, const WnRun &r, bool asked_outside) : c(cx_), p0(cx_.gslab), n0(cx_.gslab_floats)
+    GslabScope(Ctx &cx_, const WnRun &r) : c(cx_), p0(cx_.gslab), n0(cx_.gslab_floats)
     {
-        const size_t n = (r.w.slab_floats && (asked_outside || !c.fq)) ? r.w.slab_floats : 0;
+        const size_t n = (r.w.slab_floats && !c.fq) ? r.w.slab_floats : 0;
         c.gslab = n ? r.ws + r.w.slab : nullptr; c.gslab_floats = n;
     }
     ~GslabScope() { c.gslab = p0; c.gslab_floats = n0; }
 };
-static bool gate_parts_on(Ctx &cx, const WnRun &r)
+static bool gate_parts_on(const Ctx &cx, const WnRun &r)
 {
-    if (!lowrank_base(cx, r) || !gate_parts_shape(r.d) || !r.w.gpart_step || !r.L.effA || cx.probe) return false;
+    if (!lowrank_base(cx, r) || !gate_parts_shape(r.d) || !r.w.gpart_step || !r.L.effA) return false;
     if (env_sw().layer_fusion_big) return false;              // (the opt-in one-launch layer on 256 x 128 tiles has its own gate epilogue)
-    GslabScope gslab_scope(cx, r, true);
     // every layer of the pass must take a route that writes the rows, and layer 0 is not routed like the others where the start is folded
     // into it (start_fold_on: 6 chunks of K against 27 at 256 channels; the 256 x 192-tile kernel takes 16 chunks and more, and writes
     // 8-float rows only).  Layers 1 .. depth-1 differ only in their dilation, which no routing rule reads (the tap shifts are segment
-    // offsets; g192_fits and the tile counts see K, M and the columns): layer 1 answers for all of them.
-    int route0 = 0, route1 = 1;
-    cx.gate_eff = r.pk + r.L.effA; cx.gate_part = r.ws + r.w.gpart; cx.gate_prow = gate_part_prow(r.d);
-    cx.probe = &route0;
-    wn_gate_conv(cx, r, 0, 0, true);
-    if (r.d.depth > 1) {
-        cx.probe = &route1;
-        wn_gate_conv(cx, r, 1, 1, true);
-    }
-    cx.probe = nullptr; cx.gate_eff = nullptr; cx.gate_part = nullptr; cx.gate_prow = 8;
-    return route0 == 1 && route1 == 1;
+    // offsets; g192_fits and the tile counts see K, M and the columns): layer 1 answers for all of them.  (The split-K scratch a caller
+    // has attached -- Ctx::gslab -- does not change the answer: a gate conv asked for its rows is never cut along K.)
+    return route_conv(cx, wn_gate_op(cx, r, 0, 0, true, true)).part && (r.d.depth < 2 || route_conv(cx, wn_gate_op(cx, r, 1, 1, true, true)).part);
 }
 
 void wn_forward(Ctx &cx, const WnRun &r)
@@ -2200,9 +2187,9 @@ void wn_forward(Ctx &cx, const WnRun &r)
     const Geo &g = r.g;
     float *ws = r.ws;
     const bool sp = cx.prec == 2;
-    GslabScope gslab_scope(cx, r, false);                     // (scratch for a split gate conv's parts)
+    GslabScope gslab_scope(cx, r);                            // (scratch for a split gate conv's parts)
     const int nb = d.bias ? 1 : 0;
-    const SegSpec sone = d.bias ? ones_seg(cx, r, true) : SegSpec{};
+    const SegSpec sone = d.bias ? ones_fill(cx, r) : SegSpec{};
     const int cols0 = (cx.row_sel1 && g.rows > 0 ? g.B / g.rows : g.B) * g.Tt;
     const bool so = s_only_chain(cx, d) && fused_skip(d) && cols0 >= WG_FUSED_SKIP_MIN_COLS;      // residual stream as S-planes only
     // WN.start on the vector ALU in ONE launch (start_fwd_kernel, wg_thin.h) instead of an S-plane conversion + an MFMA conv on a K of 2-4
@@ -2215,14 +2202,14 @@ void wn_forward(Ctx &cx, const WnRun &r)
         ;
     if (r.start_done) {
         // (the seam launch of the flow visited before wrote h_0: same arithmetic as start_fwd_kernel below)
-        if (start_fold_on(cx, r)) run_to_splane(cx, g, r.X, d.ic, ws + r.w.XaS, r.L.kp_start);      // (layer 0 reads xa itself: wn_gate_conv)
+        if (start_fold_on(cx, r)) run_to_splane(cx, g, r.X, d.ic, ws + r.w.XaS, r.L.kp_start);      // (layer 0 reads xa itself: wn_gate_op)
     } else if (vstart) {
         StartFwdArgs a;
         memset(&a, 0, sizeof(a));
         a.X = r.X; a.W = r.pk + r.L.startN; a.ldw = r.L.ld_startN; a.C = d.C; a.ic = d.ic;
         a.H = so ? pnull() : pref(ws + r.w.H[0], d.C);
         a.HS = sref(g, ws + r.w.HS[0], d.C);
-        if (start_fold_on(cx, r)) a.XS = sref(g, ws + r.w.XaS, r.L.kp_start);      // (layer 0 reads xa itself: wn_gate_conv)
+        if (start_fold_on(cx, r)) a.XS = sref(g, ws + r.w.XaS, r.L.kp_start);      // (layer 0 reads xa itself: wn_gate_op)
         a.g = g; a.row_sel1 = cx.row_sel1;
         WG_LAUNCH(cx, start_fwd_kernel, dim3((g.T + 255) / 256, d.C / 8, cx.row_sel1 && g.rows > 0 ? g.B / g.rows : g.B), dim3(256), 0, a);
     } else {
@@ -2244,41 +2231,34 @@ void wn_forward(Ctx &cx, const WnRun &r)
         float *gate = ws + r.w.gate[(r.save || fs) ? i : 0];
         const float *gateS = ws + r.w.gateS[(r.save || fs) ? i : 0];
         // fp32 gate plane: only the on-the-fly weight-gradient kernel still reads it (backward); the S-plane feeds W_o
-        auto gate_call = [&]() {
-            if (gparts) {
-                cx.gate_eff = r.pk + r.L.effA + (size_t)i * (d.Cd / 32) * 256; cx.gate_part = ws + r.w.gpart + (size_t)i * r.w.gpart_step;
-                cx.gate_prow = gate_part_prow(d);
-            }
-            wn_gate_conv(cx, r, i, hin, r.save || fs);
-            cx.gate_eff = nullptr; cx.gate_part = nullptr; cx.gate_prow = 8;
-        };
         SegSpec sgt[2] = {{gate, d.Cd, 0, d.Cd, 0, gateS, d.Cd, 0}, sone};
         const int last = i == d.depth - 1;
+        if (fs) {
+            // residual rows only: h_{i+1} = h_i + Wres_i gate_i (the first C rows of W_o); the skip rows of all layers follow in one product
+            const ConvOp gate_op = wn_gate_op(cx, r, i, hin, true, gparts);
+            const ConvOp res_op = conv_op(g, r.pk + r.L.WoT[i], r.L.ld_WoT[i], d.C, sgt, 1 + nb, EPI_STORE, so ? pnull() : pref(Hout, d.C), pnull(), pnull(),
+                                          so ? pnull() : pref(Hin, d.C), pnull(), 0, 0, sp ? sref(g, ws + r.w.HS[hout], d.C) : snull(),
+                                          so ? sref(g, ws + r.w.HS[hin], d.C) : snull());                                   // :45-46
+            // gate conv + residual product as ONE persistent launch where the gate conv fills the chip in whole rounds (wg_layer16q.h)
+            if (!last && so && !nb && run_convlayer_g(cx, gate_op, res_op)) continue;
+            if (!last && so && !nb && run_convlayer_big(cx, ws, r.w.lsync, gate_op, res_op)) continue;
+            run_convgemm(cx, gate_op);
+            if (!last) run_convgemm(cx, res_op);
+            continue;
+        }
+        // (described when called: run_convlayer records them with Ctx::rec set, which start_fold_on and the routes read)
+        auto gate_call = [&]() { run_convgemm(cx, wn_gate_op(cx, r, i, hin, r.save, false)); };
         auto wo_call = [&]() {
             run_convgemm(cx, g, r.pk + r.L.WoT[i], r.L.ld_WoT[i], d.wo_rows(i), sgt, 1 + nb, EPI_RESSKIP, pref(Hout, d.C),
                          pref(ws + r.w.skip, d.Cs), pnull(), pref(Hin, d.C), pnull(), last ? 0 : d.C, i > 0,
                          (sp && !last) ? sref(g, ws + r.w.HS[hout], d.C) : snull());               // :45-46,104
         };
         // the whole layer as ONE launch where both products are small-grid launches (single-utterance synthesis, WaveFlow's row steps)
-        if (!fs && !r.save && !nb && run_convlayer(cx, ws, r.w.lsync, gate_call, wo_call)) continue;
-        if (fs) {
-            // residual rows only: h_{i+1} = h_i + Wres_i gate_i (the first C rows of W_o); the skip rows of all layers follow in one product
-            auto res_call = [&]() {
-                run_convgemm(cx, g, r.pk + r.L.WoT[i], r.L.ld_WoT[i], d.C, sgt, 1 + nb, EPI_STORE, so ? pnull() : pref(Hout, d.C), pnull(), pnull(),
-                             so ? pnull() : pref(Hin, d.C), pnull(), 0, 0, sp ? sref(g, ws + r.w.HS[hout], d.C) : snull(),
-                             so ? sref(g, ws + r.w.HS[hin], d.C) : snull());                                   // :45-46
-            };
-            // gate conv + residual product as ONE persistent launch where the gate conv fills the chip in whole rounds (wg_layer16q.h)
-            if (!last && so && !nb && run_convlayer_g(cx, gate_call, res_call)) continue;
-            if (!last && so && !nb && run_convlayer_big(cx, ws, r.w.lsync, gate_call, res_call)) continue;
-            gate_call();
-            if (!last) res_call();
-            continue;
-        }
+        if (!r.save && !nb && run_convlayer(cx, ws, r.w.lsync, gate_call, wo_call)) continue;
         gate_call();
         wo_call();
     }
-    if (gparts && cx.part_written - written0 != d.depth && !cx.err) cx.err = WG_ELAUNCH;      // (a gate conv took another kernel than the probe said)
+    if (gparts && cx.part_written - written0 != d.depth && !cx.err) cx.err = WG_ELAUNCH;      // (a gate conv took another kernel than gate_parts_on said)
     if (fs && lowrank_on(cx, r)) return;                      // (the end conv reads the gate planes or the partial rows: affine_source)
     if (fs) {                                                 // cum_skip = sum_i skip_i (waveglow.py:104) = [Wskip_0 .. Wskip_{d-1}] [gate_0; ..; gate_{d-1}]
         SegSpec sk[WG_MAX_SEG];
@@ -2492,7 +2472,7 @@ void wn_backward(Ctx &cx, const WnRun &r, const float *const *p, float *const *g
     const int nb = d.bias ? 1 : 0;
     WSegSpec wone = {nullptr, 32, 0, 32, 0, nullptr, 32, 0};
     if (nb) {
-        const SegSpec so1 = ones_seg(cx, r, true);
+        const SegSpec so1 = ones_fill(cx, r);
         wone.src = so1.src; wone.s = so1.s;
     }
     auto fin_bias = [&](const float *slabp, const WgradOut &wo, int row0, int rows, int col0, float *db) {
