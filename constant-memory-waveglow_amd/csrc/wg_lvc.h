@@ -9,8 +9,10 @@
 //                        and the 1x1 convs of the WN (batched over items, or summed over items for a weight gradient).
 //                        64 x 64 tiles, 16-deep K steps through LDS, 4 x 4 outputs per thread; a product of few tiles and a
 //                        long K is cut along K, its partial slices added in slice order by a second launch (gemm_splits).
-//   wg_mg_bn_*           BatchNorm1d statistics per channel row (two passes in double, LDS tree), the fused normalise + tanh
-//                        (+ residual), its backward with batch or running statistics, and the running-stat update on its own.
+//   wg_mg_bn_*           BatchNorm1d statistics per channel row (two passes in double, LDS tree; mean and 1 / std stay in double
+//                        between the launches: x - mean must not lose the low bits of a large mean, and with two values per
+//                        channel the backward is a difference of order eps), the fused normalise + tanh (+ residual), its
+//                        backward with batch or running statistics, and the running-stat update on its own.
 //   wg_mg_weight_norm*   w = g v / ||v|| per output row and its backward.
 //   wg_lvc_forward       one workgroup per (item, frame): z[2D, L] = W_f[2D, R K] . X_unfold[R K, L] with the gate in the
 //                        epilogue.  W_f is read exactly once, in 24-column slices staged in LDS (coalesced rows of
@@ -166,14 +168,14 @@ __device__ inline double block_sum(double v, double *red)
 }
 
 __global__ __launch_bounds__(256) void bn_stats_kernel(const float *x, int N, float eps, int train, const float *rmean, const float *rvar,
-                                                       float *mean, float *invstd, float *var_unb)
+                                                       double *mean, double *invstd, float *var_unb)
 {
     __shared__ double red[256];
     const int c = blockIdx.x, tid = threadIdx.x;
     if (!train) {
         if (tid == 0) {
             mean[c] = rmean[c];
-            invstd[c] = 1.0f / sqrtf(rvar[c] + eps);
+            invstd[c] = 1.0 / sqrt((double)rvar[c] + (double)eps);
             var_unb[c] = rvar[c];
         }
         return;
@@ -189,30 +191,30 @@ __global__ __launch_bounds__(256) void bn_stats_kernel(const float *x, int N, fl
     }
     q = block_sum(q, red);
     if (tid == 0) {
-        mean[c] = (float)mu;
-        invstd[c] = (float)(1.0 / sqrt(q / N + (double)eps));
+        mean[c] = mu;
+        invstd[c] = 1.0 / sqrt(q / N + (double)eps);
         var_unb[c] = N > 1 ? (float)(q / (N - 1)) : 0.f;
     }
 }
 
-__global__ __launch_bounds__(256) void bn_update_kernel(float *rmean, float *rvar, int64_t *nbt, const float *mean, const float *var_unb,
+__global__ __launch_bounds__(256) void bn_update_kernel(float *rmean, float *rvar, int64_t *nbt, const double *mean, const float *var_unb,
                                                         int C, float momentum)
 {
     const int c = blockIdx.x * 256 + threadIdx.x;
     if (c < C) {
-        rmean[c] = momentum * mean[c] + (1.f - momentum) * rmean[c];
+        rmean[c] = momentum * (float)mean[c] + (1.f - momentum) * rmean[c];
         rvar[c] = momentum * var_unb[c] + (1.f - momentum) * rvar[c];
     }
     if (c == 0 && nbt) nbt[0] += 1;
 }
 
-__global__ __launch_bounds__(256) void bn_tanh_kernel(const float *x, long long N, long long total, const float *mean, const float *invstd,
+__global__ __launch_bounds__(256) void bn_tanh_kernel(const float *x, long long N, long long total, const double *mean, const double *invstd,
                                                       const float *gamma, const float *beta, const float *res, float *s, float *sum)
 {
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
     if (i >= total) return;
     const int c = (int)(i / N);
-    float v = (x[i] - mean[c]) * invstd[c];
+    float v = (float)(((double)x[i] - mean[c]) * invstd[c]);
     if (gamma) v *= gamma[c];
     if (beta) v += beta[c];
     const float t = tanhf(v);
@@ -220,20 +222,20 @@ __global__ __launch_bounds__(256) void bn_tanh_kernel(const float *x, long long 
     if (res) sum[i] = t + res[i];
 }
 
-__global__ __launch_bounds__(256) void bn_tanh_bwd_kernel(const float *ds, const float *s, const float *x, int N, const float *mean,
-                                                          const float *invstd, const float *gamma, int train, float *dx, float *dgamma,
+__global__ __launch_bounds__(256) void bn_tanh_bwd_kernel(const float *ds, const float *s, const float *x, int N, const double *mean,
+                                                          const double *invstd, const float *gamma, int train, float *dx, float *dgamma,
                                                           float *dbeta)
 {
     __shared__ double red[256];
     const int c = blockIdx.x, tid = threadIdx.x;
     const long long o = (long long)c * N;
-    const float mu = mean[c], is = invstd[c];
+    const double mu = mean[c], is = invstd[c];
     double sd = 0.0, sdx = 0.0;
     for (int n = tid; n < N; n += 256) {
         const float t = s[o + n];
         const float dyh = ds[o + n] * (1.f - t * t);
         sd += dyh;
-        sdx += (double)dyh * ((x[o + n] - mu) * is);
+        sdx += (double)dyh * (((double)x[o + n] - mu) * is);
     }
     sd = block_sum(sd, red);
     sdx = block_sum(sdx, red);
@@ -241,13 +243,13 @@ __global__ __launch_bounds__(256) void bn_tanh_bwd_kernel(const float *ds, const
         if (dgamma) dgamma[c] = (float)sdx;
         if (dbeta) dbeta[c] = (float)sd;
     }
-    const float k = (gamma ? gamma[c] : 1.f) * is;
-    const float md = train ? (float)(sd / N) : 0.f, mdx = train ? (float)(sdx / N) : 0.f;
+    const double k = (gamma ? (double)gamma[c] : 1.0) * is;
+    const double md = train ? sd / N : 0.0, mdx = train ? sdx / N : 0.0;
     for (int n = tid; n < N; n += 256) {
         const float t = s[o + n];
         const float dyh = ds[o + n] * (1.f - t * t);
-        const float xh = (x[o + n] - mu) * is;
-        dx[o + n] = k * (dyh - md - xh * mdx);
+        const double xh = ((double)x[o + n] - mu) * is;
+        dx[o + n] = (float)(k * ((double)dyh - md - xh * mdx));
     }
 }
 
@@ -495,8 +497,8 @@ int wg_mg_gemm(const wg_mg_gemm_desc *d, const float *A, const float *B, const f
     return mg::launched();
 }
 
-int wg_mg_bn_stats(const float *x, int C, int N, float eps, int train, const float *running_mean, const float *running_var, float *mean,
-                   float *invstd, float *var_unbiased, void *stream)
+int wg_mg_bn_stats(const float *x, int C, int N, float eps, int train, const float *running_mean, const float *running_var, double *mean,
+                   double *invstd, float *var_unbiased, void *stream)
 {
     if (C < 1 || N < 1 || !mean || !invstd || !var_unbiased) return WG_EINVAL;
     if (train ? !x : (!running_mean || !running_var)) return WG_EINVAL;
@@ -505,7 +507,7 @@ int wg_mg_bn_stats(const float *x, int C, int N, float eps, int train, const flo
     return mg::launched();
 }
 
-int wg_mg_bn_update(float *running_mean, float *running_var, int64_t *num_batches_tracked, const float *mean, const float *var_unbiased,
+int wg_mg_bn_update(float *running_mean, float *running_var, int64_t *num_batches_tracked, const double *mean, const float *var_unbiased,
                     int C, float momentum, void *stream)
 {
     if (C < 1 || !running_mean || !running_var || !mean || !var_unbiased) return WG_EINVAL;
@@ -514,7 +516,7 @@ int wg_mg_bn_update(float *running_mean, float *running_var, int64_t *num_batche
     return mg::launched();
 }
 
-int wg_mg_bn_tanh(const float *x, int C, int N, const float *mean, const float *invstd, const float *gamma, const float *beta,
+int wg_mg_bn_tanh(const float *x, int C, int N, const double *mean, const double *invstd, const float *gamma, const float *beta,
                   const float *res, float *s, float *sum, void *stream)
 {
     if (!x || C < 1 || N < 1 || !mean || !invstd || !s || (res && !sum)) return WG_EINVAL;
@@ -524,7 +526,7 @@ int wg_mg_bn_tanh(const float *x, int C, int N, const float *mean, const float *
     return mg::launched();
 }
 
-int wg_mg_bn_tanh_backward(const float *ds, const float *s, const float *x, int C, int N, const float *mean, const float *invstd,
+int wg_mg_bn_tanh_backward(const float *ds, const float *s, const float *x, int C, int N, const double *mean, const double *invstd,
                            const float *gamma, int train, float *dx, float *dgamma, float *dbeta, void *stream)
 {
     if (!ds || !s || !x || C < 1 || N < 1 || !mean || !invstd || !dx) return WG_EINVAL;

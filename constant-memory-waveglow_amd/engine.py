@@ -834,7 +834,8 @@ def mg_grouped_wgrad(dy, x, G, out):
 
 def mg_bn_stats(x, eps, train, running_mean, running_var):
     Cn, N = x.shape
-    mean, invstd, var_unb = (torch.empty(Cn, dtype=torch.float32, device=x.device) for _ in range(3))
+    mean, invstd = (torch.empty(Cn, dtype=torch.float64, device=x.device) for _ in range(2))     # double: wgflow.h wg_mg_bn_stats
+    var_unb = torch.empty(Cn, dtype=torch.float32, device=x.device)
     check(_lib.lib().wg_mg_bn_stats(_p(x), Cn, N, float(eps), int(train), _p(running_mean), _p(running_var), _p(mean), _p(invstd),
                                     _p(var_unb), _stream(x.device)), "wg_mg_bn_stats")
     return mean, invstd, var_unb

@@ -84,9 +84,9 @@ const char *wg_strerror(int code);
  * layer's hand-off counters, wg_layer_apply / wg_layer_workspace_bytes, wg_wf_wn_apply; 7: wg_wf_config gained bias; 8: wg_timer_read_name,
  * wg_box_probe / wg_box_probe_bytes, wg_stat_layerg_launches, wg_stat_gate_split_launches,
  * wg_wf_wn_backward, wg_layer_backward / wg_layer_backward_workspace_bytes, wg_affine_apply / wg_affine_backward; 9: wg_reload_env,
- * wg_stat_gate_part_launches, wg_wsr_cond_pre).  A binding built against another revision must not pass its
- * structs: the Python loader compares this with its own ABI_VERSION and refuses the library otherwise. */
-#define WG_ABI_VERSION 9
+ * wg_stat_gate_part_launches, wg_wsr_cond_pre; 10: wg_mg_bn_* pass mean and 1 / std as double).  A binding built against another
+ * revision must not pass its structs: the Python loader compares this with its own ABI_VERSION and refuses the library otherwise. */
+#define WG_ABI_VERSION 10
 int wg_abi_version(void);
 /* Developer switches (WG_G192, WG_G192_SPLITK, WG_LOWRANK, WG_TW_FROM_GATE, WG_START_FOLD, WG_LAYER_G, WG_LAYER_MIN_CHUNKS, WG_LAYER_FUSION,
  * WG_LAYER_FUSION_BIG, WG_INV_SEAM: A/B switches between
@@ -364,7 +364,8 @@ int wg_affine_backward(const float *out_half, const float *log_s, const float *t
                        float *in_rebuilt, float *g_log_s, float *g_t, float *din, void *stream);
 
 /* ---- MelGlow (model/melglow.py upstream): the location-variable-convolution WN and its kernel predictor ---------------------
- * Appended to revision 9 without changing any earlier declaration.  Building blocks, each one launch (or a few) on the caller's
+ * Appended to revision 9 without changing any earlier declaration (revision 10: the BatchNorm statistics in double).  Building
+ * blocks, each one launch (or a few) on the caller's
  * stream; the composition (Predictor, NonCausalLayerLVC, WN_LVC) is driven from melglow.py.  Exact fp32 (fma chains on the vector
  * ALUs): the result does not depend on WG_PREC_*.  None of them needs a workspace: every buffer is an argument.  Every reduction
  * has a fixed order (no atomics), so a recompute reproduces its forward bit for bit. */
@@ -389,18 +390,21 @@ int wg_mg_gemm(const wg_mg_gemm_desc *d, const float *A, const float *B, const f
                void *stream);
 
 /* BatchNorm1d over rows of x[C][N] (N = B * frames).  stats: train = 1 -> batch mean, 1/sqrt(biased var + eps) and the unbiased
- * variance (sums in double, fixed order); train = 0 -> the same three from running_mean / running_var.
+ * variance (sums in double, fixed order); train = 0 -> the same three from running_mean / running_var.  mean and invstd are
+ * double[C]: tanh and tanh_backward subtract the mean from x in double, so a mean that is large against the deviation costs no
+ * accuracy, and the backward's dyh - mean(dyh) - xh mean(dyh xh), which cancels to order eps when a channel has two values, is
+ * formed in double.
  * update: running = momentum * batch + (1 - momentum) * running (the unbiased variance for running_var), ++*num_batches_tracked
  * (nullable) -- a launch of its own, so that the caller decides when the running statistics move.
  * tanh: s = tanh((x - mean) * invstd * gamma + beta), sum = s + res (res nullable; gamma / beta nullable = affine off).
  * tanh_backward: from ds (gradient of s): dx with batch statistics (train = 1) or constants (train = 0), dgamma / dbeta (nullable). */
-int wg_mg_bn_stats(const float *x, int C, int N, float eps, int train, const float *running_mean, const float *running_var, float *mean,
-                   float *invstd, float *var_unbiased, void *stream);
-int wg_mg_bn_update(float *running_mean, float *running_var, int64_t *num_batches_tracked, const float *mean, const float *var_unbiased,
+int wg_mg_bn_stats(const float *x, int C, int N, float eps, int train, const float *running_mean, const float *running_var, double *mean,
+                   double *invstd, float *var_unbiased, void *stream);
+int wg_mg_bn_update(float *running_mean, float *running_var, int64_t *num_batches_tracked, const double *mean, const float *var_unbiased,
                     int C, float momentum, void *stream);
-int wg_mg_bn_tanh(const float *x, int C, int N, const float *mean, const float *invstd, const float *gamma, const float *beta,
+int wg_mg_bn_tanh(const float *x, int C, int N, const double *mean, const double *invstd, const float *gamma, const float *beta,
                   const float *res, float *s, float *sum, void *stream);
-int wg_mg_bn_tanh_backward(const float *ds, const float *s, const float *x, int C, int N, const float *mean, const float *invstd,
+int wg_mg_bn_tanh_backward(const float *ds, const float *s, const float *x, int C, int N, const double *mean, const double *invstd,
                            const float *gamma, int train, float *dx, float *dgamma, float *dbeta, void *stream);
 
 /* weight norm over dim 0 of a [rows][cols] weight: w = g v / ||v||, and its backward (dg nullable). */

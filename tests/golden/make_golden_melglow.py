@@ -1,7 +1,7 @@
 """Generates the MelGlow fixtures tests/golden/mg/model_mg_*.npz by running the UPSTREAM REFERENCE's model/melglow.py (imported through
 ref_shim) on the CPU, on deterministic inputs and parameters from fill.py.  Build container only.
 
-    python tests/golden/make_golden_melglow.py            # the small cases (seconds)
+    python tests/golden/make_golden_melglow.py            # the small cases and the ragged one (seconds)
     python tests/golden/make_golden_melglow.py mg_full    # the shipped configuration at 8 x 22 016, as a summary (minutes)
 
 The fixtures live in their own directory, next to (not among) the WaveGlow / WaveFlow ones that make_golden.py regenerates.  Every
@@ -27,12 +27,18 @@ ARCH_SMALL = dict(flows=4, n_group=8, n_early_every=2, n_early_size=2, hop_size=
                   residual_channels=8, skip_channels=8, depth=7, radix=3, predict_channels=4, predict_layers=1, bias=False)
 ARCH_FULL = dict(flows=12, n_group=8, n_early_every=4, n_early_size=2, hop_size=256, n_mels=80, dilation_channels=48,
                  residual_channels=48, skip_channels=48, depth=7, radix=3, predict_channels=64, predict_layers=3, bias=False)
-SHAPES = {"mg_small": (2, 8 * 256), "mg_full": (8, 22016)}     # (batch, samples); frames = samples / hop
+# ragged on purpose: L = hop / n_group = 25 columns per frame, T = 125 < the last dilations, R radix = 50, 2D = 12, R != D != S, 3 input
+# channels in the last flow -- none of the LVC kernels' internal steps (24 / 16 / 32) divides anything here
+ARCH_RAGGED = dict(flows=3, n_group=8, n_early_every=2, n_early_size=2, hop_size=200, n_mels=80, dilation_channels=6,
+                   residual_channels=10, skip_channels=4, depth=8, radix=5, predict_channels=4, predict_layers=1, bias=False)
+SHAPES = {"mg_small": (2, 8 * 256), "mg_ragged": (3, 1000), "mg_full": (8, 22016)}     # (batch, samples); frames = samples / hop
 CASES = {                                                      # fixture -> (arch, parameter tag, memory_efficient, reverse_mode)
     "mg_small": (ARCH_SMALL, "mg_small/", True, False),
     "mg_small_nme": (ARCH_SMALL, "mg_small/", False, False),
     "mg_small_rm": (ARCH_SMALL, "mg_small/", True, True),
+    "mg_ragged": (ARCH_RAGGED, "mg_ragged/", True, False),
 }
+INPUT_TAG = {"mg_small": "mg_small", "mg_small_nme": "mg_small", "mg_small_rm": "mg_small", "mg_ragged": "mg_ragged"}   # SHAPES / inputs key
 
 
 def param_values(model, tag, arch):
@@ -90,8 +96,8 @@ def small_fixture(name):
     arch, tag, me, rmode = CASES[name]
     MelGlow, Loss = load_reference()
     m = build(MelGlow, arch, me, rmode, tag)
-    B, N = SHAPES["mg_small"]
-    audio, h = inputs("mg_small", B, N, arch["n_mels"], arch["hop_size"])
+    B, N = SHAPES[INPUT_TAG[name]]
+    audio, h = inputs(INPUT_TAG[name], B, N, arch["n_mels"], arch["hop_size"])
     ht = torch.from_numpy(h).requires_grad_(True)
     z, ld = m(torch.tensor(audio), ht)               # (a tensor of its own: the memory-efficient blocks free and rebuild it)
     loss = Loss(fill.SIGMA)(z, ld)

@@ -1,4 +1,5 @@
-"""MelGlow on the MI355X (-m gpu): the LVC layer and the predictor against float64 restatements written here, the whole model against
+"""MelGlow on the MI355X (-m gpu): the LVC layer and the predictor against the float64 restatements of golden/mg_ref64.py (the kernels
+one by one at ragged shapes: test_gpu_melglow_kernels.py), the whole model against
 the reference's own training steps (tests/golden/mg/, made by make_golden_melglow.py), round trips, sampling and run-to-run identity.
 
 Bars: z 1e-4 abs, loss 1e-6 abs, logdet rtol 1e-4, every gradient within 1e-4 of its tensor's max-abs, BatchNorm running statistics
@@ -8,10 +9,10 @@ import os
 import numpy as np
 import pytest
 import torch
-import torch.nn.functional as Fn
 
 import fill
 import make_golden_melglow as mgg
+from mg_ref64 import layer64, predictor64, wnorm64
 import constant_memory_waveglow_amd as cm
 from constant_memory_waveglow_amd import melglow as mg
 
@@ -24,53 +25,6 @@ Z_ATOL, LOSS_ATOL, GRAD_RTOL, STAT_RTOL = 1e-4, 1e-6, 1e-4, 1e-5
 def rel(a, b):
     a, b = a.detach().double().cpu(), torch.as_tensor(b).double().cpu()
     return float((a - b).abs().max() / max(float(b.abs().max()), 1e-30))
-
-
-# ---- float64 restatements ------------------------------------------------------------------------------------------------------
-def lvc_conv64(x, w, dilation):
-    """z[b, o, c] = sum_{r, k} w[b, c // L, o, r, k] x[b, r, c + (k - K // 2) dilation], zero outside the signal."""
-    B, R, T = x.shape
-    nf, K = w.shape[1], w.shape[-1]
-    L = T // nf
-    z = 0
-    for k in range(K):
-        src = torch.arange(T, device=x.device) + (k - K // 2) * dilation
-        ok = ((src >= 0) & (src < T)).to(x.dtype)
-        xs = x[:, :, src.clamp(0, T - 1)] * ok
-        wk = w[..., k].repeat_interleave(L, dim=1)                    # [B, T, 2D, R]
-        z = z + torch.einsum("btor,brt->bot", wk, xs)
-    return z
-
-
-def layer64(x, w, dilation, wo, R, last):
-    z = lvc_conv64(x, w, dilation)
-    D = z.size(1) // 2
-    g = torch.tanh(z[:, :D]) * torch.sigmoid(z[:, D:])
-    out = torch.einsum("od,bdt->bot", wo, g)
-    return (None, out) if last else (x + out[:, :R], out[:, R:])
-
-
-def wnorm64(g, v):
-    v2 = v.reshape(v.size(0), -1)
-    return v2 * (g.reshape(-1, 1) / v2.norm(dim=1, keepdim=True))
-
-
-def predictor64(pred, y, training):
-    """Predictor.forward in float64 with BatchNorm from torch.nn.functional on float64 copies of the buffers."""
-    bufs = {}
-
-    def bn(m, a):
-        rm, rv = m.running_mean.detach().double().clone(), m.running_var.detach().double().clone()
-        out = Fn.batch_norm(a, rm, rv, m.weight.double(), m.bias.double(), training, m.momentum, m.eps)
-        bufs[id(m)] = (rm, rv)
-        return out
-
-    G = pred.groups
-    h = torch.tanh(bn(pred.start[1], Fn.conv1d(y, pred.start[0].weight.double())))
-    for blk in pred.res_blocks:
-        a = torch.tanh(bn(blk[1], Fn.conv1d(h, blk[0].weight.double(), groups=G)))
-        h = torch.tanh(bn(blk[4], Fn.conv1d(a, blk[3].weight.double(), groups=G))) + h
-    return Fn.conv1d(h, pred.end.weight.double(), groups=G), bufs
 
 
 # ---- the LVC layer ---------------------------------------------------------------------------------------------------------------
@@ -157,11 +111,11 @@ def step(m, arch, shape_tag, h_grad=True):
     return z, ld, loss, ht
 
 
-@pytest.mark.parametrize("name", ["mg_small", "mg_small_nme", "mg_small_rm"])
+@pytest.mark.parametrize("name", ["mg_small", "mg_small_nme", "mg_small_rm", "mg_ragged"])
 def test_small_model_vs_reference(name):
     ref = np.load(os.path.join(GOLD, "model_%s.npz" % name))
     m, arch = build(name)
-    z, ld, loss, ht = step(m, arch, "mg_small")
+    z, ld, loss, ht = step(m, arch, mgg.INPUT_TAG[name])
     assert float((z.detach().cpu() - torch.from_numpy(ref["z"])).abs().max()) < Z_ATOL
     assert abs(float(loss) - float(ref["loss"])) < LOSS_ATOL
     np.testing.assert_allclose(ld.detach().cpu().numpy(), ref["logdet"], rtol=1e-4, atol=1e-7 * ref["z"].size)
@@ -210,10 +164,19 @@ def test_shipped_config_vs_reference_summary():
 # ---- properties ------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("memory_efficient", [True, False])
 def test_round_trip_infer_and_determinism(memory_efficient):
-    m, arch = build("mg_small", memory_efficient=memory_efficient)
+    round_trip_infer_and_determinism("mg_small", memory_efficient)
+
+
+@pytest.mark.parametrize("memory_efficient", [True, False])
+def test_ragged_round_trip_infer_and_determinism(memory_efficient):
+    round_trip_infer_and_determinism("mg_ragged", memory_efficient)
+
+
+def round_trip_infer_and_determinism(name, memory_efficient):
+    m, arch = build(name, memory_efficient=memory_efficient)
     m.eval()
-    B, N = mgg.SHAPES["mg_small"]
-    audio, h = mgg.inputs("mg_small", B, N, arch["n_mels"], arch["hop_size"])
+    B, N = mgg.SHAPES[name]
+    audio, h = mgg.inputs(name, B, N, arch["n_mels"], arch["hop_size"])
     ht = torch.from_numpy(h).to(DEV)
     with torch.no_grad():
         z, ld = m(torch.from_numpy(audio).to(DEV), ht)
@@ -227,8 +190,8 @@ def test_round_trip_infer_and_determinism(memory_efficient):
     m.train()
     runs = []
     for _ in range(2):
-        m2, _ = build("mg_small", memory_efficient=memory_efficient)
-        z, ld, loss, ht2 = step(m2, arch, "mg_small")
+        m2, _ = build(name, memory_efficient=memory_efficient)
+        z, ld, loss, ht2 = step(m2, arch, name)
         runs.append([z.detach().cpu(), ld.detach().cpu(), ht2.grad.cpu()] + [p.grad.cpu() for p in m2.parameters()] +
                     [b.cpu() for b in m2.buffers()])
     for a, b in zip(*runs):
