@@ -34,7 +34,7 @@ def needs_build():
 
 
 def build(force=False, verbose=False, defines=(), out=None):
-    """defines / out: developer A/B builds (tools/kbench.py), e.g. build(True, defines=["WG_OPT_X=1"], out="/tmp/x.so")"""
+    """defines / out: the instrumented build of the trace tools, e.g. build(True, defines=["WG_DBG_TRACE"], out="trace.so")"""
     if out is None and not force and not needs_build():
         return OUT
     out = out or OUT

@@ -49,15 +49,11 @@ typedef __attribute__((address_space(3))) char wgg_lds_char;
 // LDS address; it is compiler-reserved, so it is written and restored inside the statement (cdna_hip_programming.md section 5.7).
 __device__ __forceinline__ void wgg_glds16(const void *sbase, unsigned voff, unsigned lds_dst)
 {
-#if defined(WGG_DBG_NOLOAD)                               // timing build: the address work stays, nothing is fetched (results are garbage)
-    asm volatile("" ::"v"(voff), "s"(lds_dst), "s"(sbase) : "memory");
-#else
     unsigned keep;
     asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %3\n\ts_mov_b32 m0, %0"
                  : "=&s"(keep)
                  : "v"(voff), "s"(lds_dst), "s"(sbase)
                  : "memory");
-#endif
 }
 
 // Split K (xcd_items = 2, ntz = splits): a product whose tiles cannot fill the chip -- WSRGlow's gate conv, M = 512 x 6 144 columns = 64
@@ -115,34 +111,11 @@ __device__ __forceinline__ void wgg_gate_nb(const ConvGemmArgs &a, const SRef &s
         asm volatile("s_nop 15\n\ts_nop 3" : "+v"(o));
         if (live && rq < 2) wgg_st16(pb, (unsigned)(col * 32 + rq * 16), o);      // rows 4 rq .. 4 rq + 3 of column col
     }
-#if defined(WGG_OPT_UNIT16)
-    // A/B (measured, parity green, NOT adopted: 57.10 / 57.15 against 57.16 / 57.19 ms per step, layer launch 148.5 / 147.7 against
-    // 147.1 / 147.4 us -- gpurun_out/r06l: the width of the S-plane stores is not what the store drain costs, as round 2 found for the
-    // older kernel): the gate's S-plane as 16-byte stores.  Lanes l and l + 16 hold the two halves of one unit; v_permlane16_swap trades the odd
-    // 16-lane rows of the first 16-channel block's registers for the even rows of the second's: even rows then hold a whole unit of
-    // block 0, odd rows one of block 1 -- two 16-byte stores per column block instead of four 8-byte ones
-    {
-        u32x4 uh = {gh[0][0], gh[0][1], gh[1][0], gh[1][1]}, ul = {gl[0][0], gl[0][1], gl[1][0], gl[1][1]};
-        swap16_unit(uh); swap16_unit(ul);
-        const int mbp = rq & 1;                               // the block this lane's unit belongs to
-        const unsigned short *sh = s0.hi + s_index(s0, g, bb, chb, t0), *sl = sh + s0.lo_off;
-        const unsigned vo_u = (unsigned)(((2 * mbp + (rq >> 1)) * g.P + col) * 16);
-        if (live) {
-            asm volatile("global_store_dwordx4 %0, %1, %2\n\ts_nop 1" ::"v"(vo_u), "v"(uh), "s"(sh) : "memory");
-            asm volatile("global_store_dwordx4 %0, %1, %2\n\ts_nop 1" ::"v"(vo_u), "v"(ul), "s"(sl) : "memory");
-        }
-#pragma unroll
-        for (int q = 0; q < 2; ++q) {
-            const float *bt = has_t ? paddr4(a.out1, g, bb, chb + q * 16, t0) : nullptr;
-            const float *bs = has_ts ? paddr4(a.out2, g, bb, chb + q * 16, t0) : nullptr;
-            f32x4 vt, vs;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) { vt[e] = tw[4 * q + e]; vs[e] = sf[4 * q + e]; }
-            if (live && has_t) wgq_st16nt<0>(bt, vo_t, vt);
-            if (live && has_ts) wgq_st16nt<0>(bs, vo_t, vs);
-        }
-    }
-#else
+    // (tried: the gate's S-plane as 16-byte stores -- v_permlane16_swap pairs the two 16-channel blocks, two 16-byte stores per column block
+    // instead of four 8-byte ones.  Measured, parity green, not adopted: 57.10 / 57.15 against 57.16 / 57.19 ms per step, layer launch
+    // 148.5 / 147.7 against 147.1 / 147.4 us -- the width of the S-plane stores is not what the store drain costs, as round 2 found for the
+    // older kernel.  Also tried: these stores write-through ("sc1") or non-temporal ("nt").  code: git show
+    // 9da18f4:constant-memory-waveglow_amd/csrc/wg_gemm16g.h)
 #pragma unroll
     for (int mbp = 0; mbp < 2; ++mbp) {
         const float *bt = has_t ? paddr4(a.out1, g, bb, chb + mbp * 16, t0) : nullptr;
@@ -152,26 +125,13 @@ __device__ __forceinline__ void wgg_gate_nb(const ConvGemmArgs &a, const SRef &s
 #pragma unroll
         for (int e = 0; e < 4; ++e) { vt[e] = tw[4 * mbp + e]; vs[e] = sf[4 * mbp + e]; }
         const u32x2 vh = gh[mbp], vl = gl[mbp];
-#if defined(WGG_DBG_NOSTORE)                              // timing build: the epilogue's arithmetic without its stores
-        if (live && vh[0] == 0x12345u && vl[1] == 0x54321u) {
-#else
         if (live) {
-#endif
             if (has_t) wgq_st16nt<0>(bt, vo_t, vt);
             if (has_ts) wgq_st16nt<0>(bs, vo_t, vs);
-#if defined(WGG_OPT_ST_SC1)                               // experiment: write-through stores (no dirty lines left for the end-of-kernel write-back)
-            asm volatile("global_store_dwordx2 %0, %1, %2 sc1" ::"v"(vo_s), "v"(vh), "s"(sh) : "memory");
-            asm volatile("global_store_dwordx2 %0, %1, %2 sc1" ::"v"(vo_s), "v"(vl), "s"(sl) : "memory");
-#elif defined(WGG_OPT_ST_NT)
-            asm volatile("global_store_dwordx2 %0, %1, %2 nt" ::"v"(vo_s), "v"(vh), "s"(sh) : "memory");
-            asm volatile("global_store_dwordx2 %0, %1, %2 nt" ::"v"(vo_s), "v"(vl), "s"(sl) : "memory");
-#else
             wgq_st8<0>(sh, vo_s, vh);
             wgq_st8<0>(sl, vo_s, vl);
-#endif
         }
     }
-#endif
     __builtin_amdgcn_sched_barrier(0);
 }
 
@@ -184,23 +144,6 @@ __device__ __forceinline__ void wgg_store_nb(const ConvGemmArgs &a, const SRef &
     const bool live = b < g.B && t0 + col < g.T;
     const int bb = min(b, g.B - 1);
     const unsigned vo = (unsigned)(((rq >> 1) * g.P + col) * 16 + 8 * (rq & 1));
-#if defined(WGG_OPT_UNIT16)
-#pragma unroll
-    for (int mb = 0; mb < 4; mb += 2) {                       // (M is a multiple of 256 here: every row exists)
-        unsigned h0, l0, h1, l1, h2, l2, h3, l3;
-        split2(acc[mb][NBI][0], acc[mb][NBI][1], h0, l0); split2(acc[mb][NBI][2], acc[mb][NBI][3], h1, l1);
-        split2(acc[mb + 1][NBI][0], acc[mb + 1][NBI][1], h2, l2); split2(acc[mb + 1][NBI][2], acc[mb + 1][NBI][3], h3, l3);
-        u32x4 uh = {h0, h1, h2, h3}, ul = {l0, l1, l2, l3};
-        swap16_unit(uh); swap16_unit(ul);
-        const unsigned short *hb = s0.hi + s_index(s0, g, bb, mw + mb * 16, t0), *lb = hb + s0.lo_off;
-        const unsigned vo_u = (unsigned)(((2 * (rq & 1) + (rq >> 1)) * g.P + col) * 16);
-        if (live) {
-            asm volatile("global_store_dwordx4 %0, %1, %2\n\ts_nop 1" ::"v"(vo_u), "v"(uh), "s"(hb) : "memory");
-            asm volatile("global_store_dwordx4 %0, %1, %2\n\ts_nop 1" ::"v"(vo_u), "v"(ul), "s"(lb) : "memory");
-        }
-    }
-}
-#else
 #pragma unroll
     for (int mb = 0; mb < 4; ++mb) {
         const int mbase = mw + mb * 16;
@@ -212,7 +155,6 @@ __device__ __forceinline__ void wgg_store_nb(const ConvGemmArgs &a, const SRef &
         if (live && mbase + 4 * rq < a.M) { wgq_st8<0>(hb, vo, ph); wgq_st8<0>(lb, vo, pl); }
     }
 }
-#endif
 // EPI_STORE_FO, column block NBI: an fp32 plane as the only output (skip sum): the lane's 4 rows of every 16-row block are four rows of the
 // plane, 4 bytes each (a wave instruction covers 4 x 64 contiguous bytes)
 template <int NBI>
@@ -499,16 +441,8 @@ __device__ __forceinline__ void wgg_stream(const ConvGemm16sArgs &aa, char *smem
     bf16x8 Ah[2][4], Al[2][4];
     auto rd = [&](const char *q) __attribute__((always_inline)) { return *reinterpret_cast<const bf16x8 *>(q); };
 #define WGG_SB() __builtin_amdgcn_sched_barrier(0)
-#if defined(WGG_DBG_NOMFMA)                               // timing build: fragments are read, nothing is multiplied
-#define WGG_MFMA(A_, B_, C_) asm volatile("" : "+v"(C_) : "v"(A_), "v"(B_))
-#else
 #define WGG_MFMA(A_, B_, C_) C_ = __builtin_amdgcn_mfma_f32_16x16x32_bf16(A_, B_, C_, 0, 0, 0)
-#endif
-#if defined(WGG_DBG_NOBAR)                                // timing build: no barriers (results are garbage)
-#define WGG_BAR() asm volatile("" ::: "memory")
-#else
 #define WGG_BAR() do { __builtin_amdgcn_s_barrier(); asm volatile("" ::: "memory"); } while (0)
-#endif
     int ck = 0, cc = 0, ct, m0, bs = 0, gc = 0;
     tile_at(0, ct, m0);
     // the wave's six column blocks: plane row and first time step of each (a block of 16 never straddles plane rows: Tt is a multiple of 16)
@@ -553,7 +487,6 @@ __device__ __forceinline__ void wgg_stream(const ConvGemm16sArgs &aa, char *smem
         }
     };
     auto epilogue = [&]() __attribute__((always_inline)) {
-#if !defined(WGG_DBG_NOEPI)
         block_pos();
         if constexpr (EPI == EPI_GATE_SO) {
             const int chb = (m0 >> 1) + 32 * wr;                 // the wave's 64 rows = [32 tanh | 32 sigmoid] of 32 gate channels
@@ -588,9 +521,6 @@ __device__ __forceinline__ void wgg_stream(const ConvGemm16sArgs &aa, char *smem
             wgg_store_nb<2>(a, aa.s0, acc, eb[2], et[2], mw, lane); wgg_store_nb<3>(a, aa.s0, acc, eb[3], et[3], mw, lane);
             wgg_store_nb<4>(a, aa.s0, acc, eb[4], et[4], mw, lane); wgg_store_nb<5>(a, aa.s0, acc, eb[5], et[5], mw, lane);
         }
-#else
-        if (acc[0][0][0] + acc[1][1][1] + acc[2][4][2] + acc[3][5][3] == 12345.f) aa.s0.hi[lane] = 1;
-#endif
     };
 #if defined(WG_DBG_TRACE)
     // slots 0-7: inside the chunk WGG_TRACE_GC (before the TOP wait, after it, after the barrier, after blocks 0 and 2, after the MID wait,

@@ -17,9 +17,7 @@
 #pragma once
 #include "wg_gemm16q.h"
 
-#ifndef WG16H_DEPTH
 #define WG16H_DEPTH 3
-#endif
 struct Stage4 {
     u32x4 ah, al, bh, bl;
 };
@@ -190,11 +188,7 @@ __device__ __forceinline__ void convgemm16h_body(const ConvGemm16sArgs &aa, int 
         const unsigned voff_a = (unsigned)((kq * 128 + (m0 & 64) + r) * 16);
         const unsigned voff_b = (unsigned)((kq * g.P + r) * 16);
         int cur_seg = 0, cur_c = 0, chunk = 0;
-#if defined(WG_DBG_NOLOAD)
-#define WG_LD(dst, base, voff) asm volatile("" : "=v"(dst) : "v"(voff), "s"(base))
-#else
 #define WG_LD(dst, base, voff) asm volatile("global_load_dwordx4 %0, %1, %2" : "=v"(dst) : "v"(voff), "s"(base) : "memory")
-#endif
         const unsigned short *zsrc = aa.sseg[0].hi;           // plane position 0 of the first operand: always-zero halo
         auto issue = [&](Stage4 &st) {                        // exactly 4 loads in straight-line code (tools/check_asm_loads.py)
             const bool live = chunk < nchunks;
@@ -268,11 +262,7 @@ __device__ __forceinline__ void convgemm16h_body(const ConvGemm16sArgs &aa, int 
         f.bh = rd(sb + 2 * AIMG + bo); f.bl = rd(sb + 2 * AIMG + BIMG + bo);
     };
     if (EPI == EPI_STORE || EPI == EPI_RESSKIP) {
-#if !defined(WG_OPT_NO_EPI_BATCH)
         conv_acc_init_a<EPI, IN_MEMORY>(a, aa.saux, aa.img, acc, t0, m0, b, wc, lane);
-#else
-        conv_acc_init_q<EPI, 1>(a, aa.saux, acc, t0, m0, b, 0, wc, lane);
-#endif
     } else {
 #pragma unroll
         for (int i = 0; i < 4; ++i)
@@ -294,9 +284,9 @@ __device__ __forceinline__ void convgemm16h_body(const ConvGemm16sArgs &aa, int 
         fetch(fn, smem + ((c & 1) ^ 1) * BUF);
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-        for (int mb = 0; mb < 4; ++mb) if (!TwoP<EPI>::no_alo) acc[mb][0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(f.al[mb], f.bh, acc[mb][0], 0, 0, 0);
+        for (int mb = 0; mb < 4; ++mb) acc[mb][0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(f.al[mb], f.bh, acc[mb][0], 0, 0, 0);
 #pragma unroll
-        for (int mb = 0; mb < 4; ++mb) if (!TwoP<EPI>::no_blo) acc[mb][0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(f.ah[mb], f.bl, acc[mb][0], 0, 0, 0);
+        for (int mb = 0; mb < 4; ++mb) acc[mb][0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(f.ah[mb], f.bl, acc[mb][0], 0, 0, 0);
 #pragma unroll
         for (int mb = 0; mb < 4; ++mb) acc[mb][0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(f.ah[mb], f.bh, acc[mb][0], 0, 0, 0);
         __builtin_amdgcn_sched_barrier(0);
@@ -309,10 +299,8 @@ __device__ __forceinline__ void convgemm16h_body(const ConvGemm16sArgs &aa, int 
     if (c < nchunks) step(f0, f1, c);
     for (int c = nchunks; c < nbar; ++c) WG16W_BAR();         // the loaders' spare iterations
     WGH_TRACE(2);
-#if !defined(WG_OPT_NO_EPI_BATCH)
     if (EPI == EPI_STORE || EPI == EPI_RESSKIP) conv_epilogue_a<EPI, IN_MEMORY>(a, aa.s0, acc, t0, m0, b, wc, lane);
     else
-#endif
         conv_epilogue_q<EPI, 1>(a, aa.s0, acc, t0, m0, b, 0, wc, lane);
     WGH_TRACE(3);
 }

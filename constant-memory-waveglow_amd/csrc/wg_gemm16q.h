@@ -39,11 +39,6 @@ __device__ __forceinline__ int wg16q_off(int row, int kg) { return row * WG16Q_R
 // stored-activation forward, read once by the gate backward): they are kept CHANNEL-INTERLEAVED, [b][c / 4][t][4] fp32, so that the
 // four rows a lane owns at one column are ONE 16-byte unit -- a wave's access is 4 x 256 contiguous bytes instead of 16 x 64.  (In the
 // planar layout both sides moved 4 bytes per lane and instruction: the gate backward, bound by these bytes, ran at 3.7 TB/s.)
-#if !defined(WG_OPT_PLANAR_TS)
-#define WG_TS_INTERLEAVED 1
-#else
-#define WG_TS_INTERLEAVED 0
-#endif
 __device__ __forceinline__ float *paddr4(const PRef &r, const Geo &g, int b, int ch, int t)     // ch: a multiple of 4
 {
     return r.p + (((size_t)b * (r.Cp >> 2) + ((r.ch0 + ch) >> 2)) * g.P + g.H + t) * 4;
@@ -51,55 +46,16 @@ __device__ __forceinline__ float *paddr4(const PRef &r, const Geo &g, int b, int
 // S-plane units and the accumulator layout.  A lane of the 16 x 16 MFMA output owns rows 4 rq .. 4 rq + 3 (rq = lane >> 4) of one column:
 // HALF a 16-byte unit; lanes l and l + 16 own the two halves of the same unit.  As 8-byte accesses a wave instruction touches every
 // 64-byte line twice (once from each 16-lane row): the launches bound by these bytes ran at 3-4 TB/s (the residual conv spent 34 of its
-// 38 us on them: tools/experiments/shape_ab.sh).  v_permlane16_swap exchanges the odd 16-lane rows of one register with the even rows of
-// another, so two column blocks nb0, nb1 pair up: even rows move the WHOLE unit of column block nb0, odd rows that of nb1 -- one 16-byte
-// access per lane instead of two 8-byte ones, 512 contiguous bytes per channel group and instruction.
-// MEASURED AND NOT ADOPTED (-DWG_OPT_UNIT16; parity green): the residual conv went from 38.3 to 40.8 us -- the width of these accesses
-// is not what makes them slow.
-//   store: x = the lane's piece of nb0, y = its piece of nb1  ->  (x', y') = swap(x, y) is the unit the lane stores, in that order;
-//   load:  the lane loads a unit (lo8, hi8)                    ->  (x, y) = swap(lo8, hi8) are its pieces of nb0 and nb1.
-// Must be executed by ALL lanes (no divergence around it); predicate only the memory access.
-__device__ __forceinline__ void swap16_unit(u32x4 &u)      // words (0, 2) and (1, 3) of a unit
-{
-    const u32x2 r0 = __builtin_amdgcn_permlane16_swap(u[0], u[2], false, false);
-    const u32x2 r1 = __builtin_amdgcn_permlane16_swap(u[1], u[3], false, false);
-    u[0] = r0[0]; u[2] = r0[1]; u[1] = r1[0]; u[3] = r1[1];
-}
+// 38 us on them).  tried: whole 16-byte units per lane -- v_permlane16_swap pairs two column blocks, one 16-byte access instead of two
+// 8-byte ones, 512 contiguous bytes per channel group and instruction.  Measured and not adopted (parity green): the residual conv went
+// from 38.3 to 40.8 us -- the width of these accesses is not what makes them slow (code: git show
+// 9da18f4:constant-memory-waveglow_amd/csrc/wg_gemm16q.h, swap16_unit).
 template <int EPI, int NB>
 __device__ __forceinline__ void conv_acc_init_q(const ConvGemmArgs &a, const SRef &saux, f32x4 (&acc)[4][NB], int t0, int m0, int b, int wr, int wc,
                                                 int lane)
 {
     const Geo g = a.g;
     const int col = lane & 15, rq = lane >> 4;
-#if defined(WG_OPT_UNIT16)
-    if constexpr (EPI == EPI_STORE && NB >= 2) {
-        if (saux.hi) {
-#pragma unroll
-            for (int mb = 0; mb < 4; ++mb) {
-                const int mu = m0 + wr * 64 + mb * 16 + 8 * (rq >> 1);            // first row of the lane's unit
-#pragma unroll
-                for (int nb = 0; nb < NB; nb += 2) {
-                    const int t = t0 + wc * (16 * NB) + (nb + ((rq & 1))) * 16 + col;   // even rows: column block nb, odd rows: nb + 1
-                    u32x4 uh = {0u, 0u, 0u, 0u}, ul = {0u, 0u, 0u, 0u};
-                    if (t < g.T && mu < a.M) {
-                        const size_t i = s_index(saux, g, b, mu, t);
-                        uh = *reinterpret_cast<const u32x4 *>(saux.hi + i);
-                        ul = *reinterpret_cast<const u32x4 *>(saux.hi + saux.lo_off + i);
-                    }
-                    swap16_unit(uh); swap16_unit(ul);
-#pragma unroll
-                    for (int q = 0; q < 2; ++q) {                                 // q = 0: the piece of nb (words 0, 1), q = 1: of nb + 1 (words 2, 3)
-                        acc[mb][nb + q][0] = __uint_as_float(uh[2 * q] << 16) + __uint_as_float(ul[2 * q] << 16);
-                        acc[mb][nb + q][1] = __uint_as_float(uh[2 * q] & 0xffff0000u) + __uint_as_float(ul[2 * q] & 0xffff0000u);
-                        acc[mb][nb + q][2] = __uint_as_float(uh[2 * q + 1] << 16) + __uint_as_float(ul[2 * q + 1] << 16);
-                        acc[mb][nb + q][3] = __uint_as_float(uh[2 * q + 1] & 0xffff0000u) + __uint_as_float(ul[2 * q + 1] & 0xffff0000u);
-                    }
-                }
-            }
-            return;
-        }
-    }
-#endif
     if ((EPI == EPI_STORE || EPI == EPI_STORE_SO) && saux.hi) {
         // the value to accumulate into comes as an S-plane: a lane's 4 rows of one column are exactly one half unit (8 bytes) of the hi
         // array and one of the lo array; x = hi + lo (the fp32 plane of such a tensor is then never written nor read)
@@ -154,14 +110,12 @@ __device__ __forceinline__ void conv_acc_init_q(const ConvGemmArgs &a, const SRe
 }
 
 // 8-byte stores of one row block's column blocks: base (scalar) + voff (the lane's constant byte offset) + 256 * nb
+// (tried: these S-plane stores write-through, "sc1" -- fewer dirty lines for the end-of-kernel write-back: the kernel boundary costs
+// ~1.5 us + dirty bytes / 6 TB/s; not adopted -- code: git show 9da18f4:constant-memory-waveglow_amd/csrc/wg_gemm16q.h)
 template <int OFF>
 __device__ __forceinline__ void wgq_st8(const unsigned short *base, unsigned voff, const u32x2 &v)
 {
-#if defined(WG_OPT_ST_SC1)     // experiment: write-through S-plane stores -- fewer dirty lines for the end-of-kernel write-back (the kernel boundary costs
-    asm volatile("global_store_dwordx2 %0, %1, %2 offset:%3 sc1" ::"v"(voff), "v"(v), "s"(base), "n"(OFF) : "memory");      // ~1.5 us + dirty bytes / 6 TB/s)
-#else
     asm volatile("global_store_dwordx2 %0, %1, %2 offset:%3" ::"v"(voff), "v"(v), "s"(base), "n"(OFF) : "memory");
-#endif
 }
 template <int OFF>
 __device__ __forceinline__ void wgq_st16nt(const float *base, unsigned voff, const f32x4 &v)
@@ -366,33 +320,20 @@ __device__ __forceinline__ void conv_epilogue_q(const ConvGemmArgs &a, const SRe
                 if (b2) {
                     // (non-temporal: the saved tanh / sigmoid planes are read once, by the gate backward of this layer, 15 layer
                     // launches later: kept out of L2's way, -0.45 ms per training step; tanh only where out1 is given)
-#if WG_TS_INTERLEAVED
                     const int chq = chb + mbp * 16 + 4 * rq;
                     f32x4 vt, vs;
 #pragma unroll
                     for (int e = 0; e < 4; ++e) { vt[e] = tw[4 * mbp + e]; vs[e] = sf[4 * mbp + e]; }
                     if (b1) __builtin_nontemporal_store(vt, reinterpret_cast<f32x4 *>(paddr4(a.out1, g, b, chq, t0 + (int)tl)));
                     __builtin_nontemporal_store(vs, reinterpret_cast<f32x4 *>(paddr4(a.out2, g, b, chq, t0 + (int)tl)));
-#else
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        if (b1) __builtin_nontemporal_store(tw[4 * mbp + e], &b1[off + (unsigned)e * (unsigned)g.P]);
-                        __builtin_nontemporal_store(sf[4 * mbp + e], &b2[off + (unsigned)e * (unsigned)g.P]);
-                    }
-#endif
                 }
                 u32x2 vh, vl;
                 unsigned hh, ll;
                 split2(gv[4 * mbp], gv[4 * mbp + 1], hh, ll); vh[0] = hh; vl[0] = ll;
                 split2(gv[4 * mbp + 2], gv[4 * mbp + 3], hh, ll); vh[1] = hh; vl[1] = ll;
                 const unsigned so = (unsigned)(2 * mbp + (rq >> 1)) * s_grp + tl * 8u + (unsigned)(4 * (rq & 1));
-                if (WG_OPT_NT_S & 4) {
-                    __builtin_nontemporal_store(vh, reinterpret_cast<u32x2 *>(sh + so));
-                    __builtin_nontemporal_store(vl, reinterpret_cast<u32x2 *>(sl + so));
-                } else {
-                    *reinterpret_cast<u32x2 *>(sh + so) = vh;
-                    *reinterpret_cast<u32x2 *>(sl + so) = vl;
-                }
+                *reinterpret_cast<u32x2 *>(sh + so) = vh;
+                *reinterpret_cast<u32x2 *>(sl + so) = vl;
             }
             __builtin_amdgcn_sched_barrier(0);                   // eight outputs at a time
         }
@@ -401,7 +342,7 @@ __device__ __forceinline__ void conv_epilogue_q(const ConvGemmArgs &a, const SRe
     if (EPI == EPI_DGATE_SO) {
         // EPI_DGATE with hand-issued memory instructions.  The compiler's form issued a row block's eight 16-byte tanh / sigmoid loads
         // two at a time, each pair behind a full drain (a fresh 64-bit address pair per load, and this part may read an address register
-        // late): five round trips per block, four blocks per tile -- 49 of the launch's 82 us (tools/experiments/shape_ab.sh).  Here a
+        // late): five round trips per block, four blocks per tile -- 49 of the launch's 82 us.  Here a
         // block's loads are scalar base + ONE constant lane offset + immediate: issued back to back, one round trip per block; the
         // S-plane stores likewise (see EPI_STORE_SO).
         const unsigned vo_t = (unsigned)((rq * g.P + col) * 16), vo_s = (unsigned)(((rq >> 1) * g.P + col) * 16 + 8 * (rq & 1));
@@ -471,11 +412,7 @@ __device__ __forceinline__ void conv_epilogue_q(const ConvGemmArgs &a, const SRe
     if (EPI == EPI_DGATE) {
         // The auxiliary loads (tanh / sigmoid of the forward gate) of one 16-row block at a time, then combine and store it.  (All 128
         // values loaded first took the kernel to 210 VGPRs, i.e. ONE workgroup per CU for a launch bound by these bytes.)
-#if defined(WG_OPT_DGATE_ALL)
-        constexpr int MBS = 4;
-#else
         constexpr int MBS = 1;
-#endif
 #pragma unroll
         for (int mb0 = 0; mb0 < 4; mb0 += MBS) {
             f32x4 ax[MBS][NB], ay[MBS][NB];
@@ -486,7 +423,6 @@ __device__ __forceinline__ void conv_epilogue_q(const ConvGemmArgs &a, const SRe
 #pragma unroll
                 for (int nb = 0; nb < NB; ++nb) {
                     const int tl = wc * (16 * NB) + nb * 16 + col;
-#if WG_TS_INTERLEAVED
                     // (non-temporal, like the stores that saved them: this is their only use; M is a multiple of 4 here)
                     f32x4 vx = {0.f, 0.f, 0.f, 0.f}, vy = {0.f, 0.f, 0.f, 0.f};
                     if (t0 + tl < g.T && mbase + 4 * rq < a.M) {
@@ -503,16 +439,6 @@ __device__ __forceinline__ void conv_epilogue_q(const ConvGemmArgs &a, const SRe
                     }
                     ax[q][nb] = vx; ay[q][nb] = vy;
                     (void)p0; (void)p1;
-#else
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        const unsigned off = (unsigned)(4 * rq + e) * (unsigned)g.P + (unsigned)tl;
-                        float x = 0.f, y = 0.f;
-                        // (non-temporal, like the stores that saved them: this is their only use)
-                        if (t0 + tl < g.T && mbase + 4 * rq + e < a.M) { x = __builtin_nontemporal_load(&p0[off]); y = __builtin_nontemporal_load(&p1[off]); }
-                        ax[q][nb][e] = x; ay[q][nb][e] = y;
-                    }
-#endif
                 }
             }
             __builtin_amdgcn_sched_barrier(0);
@@ -534,19 +460,18 @@ __device__ __forceinline__ void conv_epilogue_q(const ConvGemmArgs &a, const SRe
                             *paddr(a.out0, g, b, a.nsplit + m + e, t) = o2[e];
                         }
                     }
-                    s_store4<(WG_OPT_NT_S & 2) != 0>(s0, g, b, m, t, o);
-                    s_store4<(WG_OPT_NT_S & 2) != 0>(s0, g, b, a.nsplit + m, t, o2);
+                    s_store4(s0, g, b, m, t, o);
+                    s_store4(s0, g, b, a.nsplit + m, t, o2);
                 }
             __builtin_amdgcn_sched_barrier(0);
         }
         return;
     }
     // EPI_STORE / EPI_RESSKIP: the auxiliary values were the accumulators' initial value (conv_acc_init_q): stores only
-#if !defined(WG_OPT_NO_EPI_BATCH) && !defined(WG_OPT_UNIT16)
     // S-plane only (the residual stream and its gradient, s_only_chain): every store of the tile issued back to back.  On this part a
     // vector-memory instruction may read its address registers LATE, so the compiler drains vmcnt before anything overwrites a register
     // of a store in flight: with one address computation per store, each store waited for the previous one to leave -- nine full drains
-    // per tile (the residual conv spent 16 of its 38 us there, tools/experiments/shape_ab.sh).  Here the stores are hand-issued: scalar
+    // per tile (the residual conv spent 16 of its 38 us there).  Here the stores are hand-issued: scalar
     // base + ONE constant 32-bit lane offset + immediate (column blocks are 256 bytes apart) -- no address register is ever rewritten,
     // nothing drains, and the tile's stores leave while the next tile is already being multiplied.
     if (EPI == EPI_STORE_FO) {                                  // fp32 plane only: four constant lane offsets (the lane's four rows), column blocks 64 bytes apart
@@ -590,7 +515,6 @@ __device__ __forceinline__ void conv_epilogue_q(const ConvGemmArgs &a, const SRe
         }
         return;
     }
-#endif
 #pragma unroll
     for (int mb = 0; mb < 4; ++mb) {
         const int mbase = m0 + wr * 64 + mb * 16;
@@ -608,34 +532,8 @@ __device__ __forceinline__ void conv_epilogue_q(const ConvGemmArgs &a, const SRe
                 o[e] = acc[mb][nb][e];
                 if (base && m + e < a.M) base[(unsigned)(4 * rq + e) * (unsigned)g.P + (unsigned)tl] = o[e];
             }
-#if defined(WG_OPT_UNIT16)
-            if constexpr (NB >= 2) continue;                 // (the S-plane goes out below, two column blocks at a time)
-#endif
-            if (res && s0.hi) s_store4<(WG_OPT_NT_S & 1) != 0>(s0, g, b, m, t, o);
+            if (res && s0.hi) s_store4(s0, g, b, m, t, o);
         }
-#if defined(WG_OPT_UNIT16)
-        if constexpr (NB >= 2) {
-            if (res && s0.hi) {                              // (wave uniform: every lane takes part in the swaps)
-                const int mu = mbase + 8 * (rq >> 1);
-#pragma unroll
-                for (int nb = 0; nb < NB; nb += 2) {
-                    u32x4 uh, ul;
-                    unsigned hh, ll;
-                    split2(acc[mb][nb][0], acc[mb][nb][1], hh, ll); uh[0] = hh; ul[0] = ll;
-                    split2(acc[mb][nb][2], acc[mb][nb][3], hh, ll); uh[1] = hh; ul[1] = ll;
-                    split2(acc[mb][nb + 1][0], acc[mb][nb + 1][1], hh, ll); uh[2] = hh; ul[2] = ll;
-                    split2(acc[mb][nb + 1][2], acc[mb][nb + 1][3], hh, ll); uh[3] = hh; ul[3] = ll;
-                    swap16_unit(uh); swap16_unit(ul);
-                    const int t = t0 + wc * (16 * NB) + (nb + (rq & 1)) * 16 + col;
-                    if (t < g.T && mu < a.M) {
-                        const size_t i = s_index(s0, g, b, mu, t);
-                        *reinterpret_cast<u32x4 *>(s0.hi + i) = uh;
-                        *reinterpret_cast<u32x4 *>(s0.hi + s0.lo_off + i) = ul;
-                    }
-                }
-            }
-        }
-#endif
     }
 }
 
@@ -718,9 +616,6 @@ __global__ __launch_bounds__(512 * MG) void convgemm16q_kernel(const ConvGemm16s
     if (wave >= 4 * MG) {
         // ------------------------------- loader waves (as convgemm16w_kernel; only the LDS destination differs) -------------------------------
         const int lt = tid - 256 * MG;
-#if defined(WG_OPT_LOADER_PRIO)
-        __builtin_amdgcn_s_setprio(WG_OPT_LOADER_PRIO);      // experiment: the loaders' few instructions never queue behind the compute waves
-#endif
         // (CG2, 512 loader lanes: B units (column lt & 255, k-groups lt >> 8 and + 2) of the 256-column image)
         const int bt = CG2 ? (lt & 255) : NI == 2 ? (lt & 127) : (lt & 63), cg0 = CG2 ? (lt >> 8) : NI == 2 ? (lt >> 7) : (lt >> 6);     // B unit: position, k-group
         const int nil = aa.tap_il * aa.tap_chunks;            // chunks walked interleaved over the taps (ConvGemm16sArgs::tap_il; 0: none)
@@ -737,21 +632,10 @@ __global__ __launch_bounds__(512 * MG) void convgemm16q_kernel(const ConvGemm16s
         constexpr int A_NEXT = MG == 2 ? 4096 : 2048;         // elements from a lane's first A piece to its second
         const int b_off[2] = {wg16q_off(bt, cg0), wg16q_off(bt, (cg0 + 2) & 3)};
         const unsigned voff_b = (unsigned)((cg0 * g.P + bt) * 16);
-#if defined(WG_DBG_NOLOAD)
-#define WG_LD(dst, base, voff) asm volatile("" : "=v"(dst) : "v"(voff), "s"(base))
-#else
 #define WG_LD(dst, base, voff) asm volatile("global_load_dwordx4 %0, %1, %2" : "=v"(dst) : "v"(voff), "s"(base) : "memory")
-#endif
-        // EXPERIMENT -DWG_OPT_A_POLICY=1 (sc1) / 2 (nt): the WEIGHT images fetched past the CU's L1 -- a workgroup reads its A chunks once,
-        // while the taps of a layer re-read overlapping windows of the activation planes a few chunks apart (tap_il): an L1 that is not
-        // flushed by the weight stream could serve those
-#if defined(WG_OPT_A_POLICY) && WG_OPT_A_POLICY == 1 && !defined(WG_DBG_NOLOAD)
-#define WG_LDA(dst, base, voff) asm volatile("global_load_dwordx4 %0, %1, %2 sc1" : "=v"(dst) : "v"(voff), "s"(base) : "memory")
-#elif defined(WG_OPT_A_POLICY) && WG_OPT_A_POLICY == 2 && !defined(WG_DBG_NOLOAD)
-#define WG_LDA(dst, base, voff) asm volatile("global_load_dwordx4 %0, %1, %2 nt" : "=v"(dst) : "v"(voff), "s"(base) : "memory")
-#else
-#define WG_LDA(dst, base, voff) WG_LD(dst, base, voff)
-#endif
+        // (tried: the WEIGHT images fetched past the CU's L1, "sc1" or "nt" -- a workgroup reads its A chunks once, while the taps of a
+        // layer re-read overlapping windows of the activation planes a few chunks apart (tap_il): an L1 that is not flushed by the weight
+        // stream could serve those; not adopted -- code: git show 9da18f4:constant-memory-waveglow_amd/csrc/wg_gemm16q.h, WG_LDA)
         // (measured: the non-temporal policy -- "nt" -- on the activation stream costs 7 % of a training step: the m-tiles of a column
         // tile and the taps of a layer re-read those lines from L2)
         const unsigned short *zsrc = aa.sseg[0].hi;           // plane position 0 of the first operand: always-zero halo
@@ -772,22 +656,18 @@ __global__ __launch_bounds__(512 * MG) void convgemm16q_kernel(const ConvGemm16s
                 rowok = r >= 0 && r < g.rows;
                 bsrc = ss.per_item ? item : b + ss.row_off;
             }
-#if defined(WG_DBG_TAPB)       // timing experiment only (results are garbage): the B operand of every tap but the first is not fetched -- what a
-            const bool blive = live && rowok && !(il && sgi % WG_DBG_TAPB != 0), full = blive && (nch - ci > 16);      // B window held in LDS across the taps could win at most
-#else
             const bool blive = live && rowok, full = blive && (nch - ci > 16);
-#endif
             const unsigned short *ih = aa.img + ((size_t)chi * a.lda + m0) * WG16_BK, *il_ = ih + aa.img_stride;
             const unsigned short *row0 = ss.hi + ((size_t)bsrc * (ss.Cp >> 3) + ((ss.ch0 + ci) >> 3)) * g.P * 8;
             const unsigned short *pa0 = live ? ih : zsrc, *pa1 = live ? ih + A_NEXT : zsrc;
             const unsigned short *pl0 = live ? il_ : zsrc, *pl1 = live ? il_ + A_NEXT : zsrc;
             const unsigned va = live ? voff_a : 0u;
             if constexpr (M64 || CG2) {
-                WG_LDA(st.ah[0], pa0, va);   WG_LDA(st.al[0], pl0, va);
+                WG_LD(st.ah[0], pa0, va);   WG_LD(st.al[0], pl0, va);
                 (void)pa1; (void)pl1;
             } else {
-                WG_LDA(st.ah[0], pa0, va);   WG_LDA(st.ah[1], pa1, va);
-                WG_LDA(st.al[0], pl0, va);   WG_LDA(st.al[1], pl1, va);
+                WG_LD(st.ah[0], pa0, va);   WG_LD(st.ah[1], pa1, va);
+                WG_LD(st.al[0], pl0, va);   WG_LD(st.al[1], pl1, va);
             }
             if constexpr ((NI == 2 && MG == 1) || CG2) {
                 const unsigned short *b0 = row0 + (size_t)(g.H + t0 + shift) * 8, *b0l = b0 + ss.lo_off;
@@ -818,7 +698,6 @@ __global__ __launch_bounds__(512 * MG) void convgemm16q_kernel(const ConvGemm16s
             }
         };
 #undef WG_LD
-#undef WG_LDA
         auto write = [&](const Stage &st, int buf) {
             char *sb = smem + buf * BUF;
 #pragma unroll
@@ -891,11 +770,6 @@ __global__ __launch_bounds__(512 * MG) void convgemm16q_kernel(const ConvGemm16s
             for (int i = 0; i < 4; ++i) { ah[i] = rd(pa + i * 1024); al[i] = rd(pa + AIMG + i * 1024); }
             bh[0] = rd(pb); bl[0] = rd(pb + BIMG);
         }
-#if defined(WG_DBG_NOMFMA)
-        for (int c = 0; c < nchunks; ++c, ++gc)
-            if (gc + 1 < total || !(total & 1)) WG16W_BAR();
-        if (false)
-#endif
         for (int c = 0; c < nchunks; ++c, ++gc) {
             const char *pb = smem + (gc & 1) * BUF + 2 * AIMG + bo;
             const char *na = smem + ((gc & 1) ^ 1) * BUF + ao, *nb_ = smem + ((gc & 1) ^ 1) * BUF + 2 * AIMG + bo;
@@ -911,8 +785,8 @@ __global__ __launch_bounds__(512 * MG) void convgemm16q_kernel(const ConvGemm16s
                 WGQ_SB();
 #pragma unroll
                 for (int mb = 0; mb < 4; ++mb) {
-                    if (!TwoP<EPI>::no_alo) acc[mb][nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al[mb], bh[cur], acc[mb][nb], 0, 0, 0);
-                    if (!TwoP<EPI>::no_blo) acc[mb][nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[mb], bl[cur], acc[mb][nb], 0, 0, 0);
+                    acc[mb][nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al[mb], bh[cur], acc[mb][nb], 0, 0, 0);
+                    acc[mb][nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[mb], bl[cur], acc[mb][nb], 0, 0, 0);
                     acc[mb][nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[mb], bh[cur], acc[mb][nb], 0, 0, 0);
                     if (mb == 0) {
                         // the next group's B is requested BEHIND this group's first MFMAs: everything those wait for was requested a
@@ -935,19 +809,9 @@ __global__ __launch_bounds__(512 * MG) void convgemm16q_kernel(const ConvGemm16s
             }
         }
         WGQ_TRACE(2 + 2 * k);
-#if defined(WG_DBG_NOEPI)
-        if (acc[0][0][0] + acc[1][0][0] + acc[2][NB - 1][1] + acc[3][NB - 1][3] == 12345.f) a.out0.p[lane] = 1.f;
-#else
         int le = lane;
         if (PERSIST) asm volatile("" : "+v"(le)::"memory");
-#if defined(WG_OPT_EPI_PRIO)
-        __builtin_amdgcn_s_setprio(WG_OPT_EPI_PRIO);         // experiment: the epilogue's VALU / store issue ahead of the co-resident workgroup's waves
-#endif
         conv_epilogue_q<EPI, NB>(a, aa.s0, acc, t0, m0, b, wr, wc, le, aa.saux, aa.eff, aa.part, aa.prow);
-#if defined(WG_OPT_EPI_PRIO)
-        __builtin_amdgcn_s_setprio(0);
-#endif
-#endif
         WGQ_TRACE(3 + 2 * k);
         if (PERSIST) WGQ_SB();
     };

@@ -15,12 +15,8 @@
 #include "wg_gemm16.h"
 
 // 4 consecutive channels (c multiple of 4) of one time step
-// EXPERIMENT -DWG_OPT_NT_S=<mask>: S-plane stores of the conv epilogues with the non-temporal policy (1: store / residual, 2: gate
-// backward, 4: gate conv)
-#if !defined(WG_OPT_NT_S)
-#define WG_OPT_NT_S 0
-#endif
-template <bool NT = false>
+// (tried: the non-temporal policy on these stores of the conv epilogues -- store / residual, gate backward, gate conv; not adopted --
+// code: git show 9da18f4:constant-memory-waveglow_amd/csrc/wg_gemm16s.h)
 __device__ __forceinline__ void s_store4(const SRef &r, const Geo &g, int b, int c, int t, const float (&v)[4])
 {
     u32x2 h, l;
@@ -28,13 +24,8 @@ __device__ __forceinline__ void s_store4(const SRef &r, const Geo &g, int b, int
     split2(v[0], v[1], hh, ll); h[0] = hh; l[0] = ll;
     split2(v[2], v[3], hh, ll); h[1] = hh; l[1] = ll;
     const size_t i = s_index(r, g, b, c, t);
-    if (NT) {
-        __builtin_nontemporal_store(h, reinterpret_cast<u32x2 *>(r.hi + i));
-        __builtin_nontemporal_store(l, reinterpret_cast<u32x2 *>(r.hi + r.lo_off + i));
-    } else {
-        *reinterpret_cast<u32x2 *>(r.hi + i) = h;
-        *reinterpret_cast<u32x2 *>(r.hi + r.lo_off + i) = l;
-    }
+    *reinterpret_cast<u32x2 *>(r.hi + i) = h;
+    *reinterpret_cast<u32x2 *>(r.hi + r.lo_off + i) = l;
 }
 
 // Two 8-byte half units -> one 16-byte unit per lane.  In the MFMA accumulator layout lanes l and l + 32 own channels 4h .. 4h+3
@@ -78,19 +69,9 @@ __global__ void to_splane_kernel(PRef src, int nvalid, SRef dst, Geo g)
 // ------------------------------------------------------------------------------------------------
 // convgemm16s: A from the pre-split weight images, B from S-planes
 // ------------------------------------------------------------------------------------------------
-// EXPERIMENT -DWG_OPT_2P=<mask>: drop one cross term of the split product a b ~ a_lo b_hi + a_hi b_lo + a_hi b_hi in a class of products (the
-// error table in DESIGN.md section 4b; the default build multiplies all three everywhere).  Bits: 1 gate conv without a_lo b_hi (the
-// weights' low half), 2 gate conv without a_hi b_lo (the activations' low half), 4 store / residual / data-gradient convs without the
-// weights' low half, 8 gate backward without the weights' low half, 16 weight gradient without the low half of its A operand (the
-// gradient planes), 32 weight gradient without the low half of its B operand (the activations).
-#if !defined(WG_OPT_2P)
-#define WG_OPT_2P 0
-#endif
-template <int EPI> struct TwoP {
-    static constexpr bool no_alo = (EPI == EPI_GATE && (WG_OPT_2P & 1)) || ((EPI == EPI_STORE || EPI == EPI_STORE_SO || EPI == EPI_STORE_FO || EPI == EPI_RESSKIP) && (WG_OPT_2P & 4)) ||
-                                   ((EPI == EPI_DGATE || EPI == EPI_DGATE_SO) && (WG_OPT_2P & 8));
-    static constexpr bool no_blo = EPI == EPI_GATE && (WG_OPT_2P & 2);
-};
+// Every product multiplies all three terms of the split product a b ~ a_lo b_hi + a_hi b_lo + a_hi b_hi.  tried: dropping one cross term
+// in a class of products (gate conv, store / residual / data-gradient convs, gate backward, either operand of the weight gradient): the
+// error table in DESIGN.md section 4b (code: git show 9da18f4:constant-memory-waveglow_amd/csrc/wg_gemm16s.h, struct TwoP).
 struct SSeg {
     const unsigned short *hi;
     size_t lo_off;
@@ -150,8 +131,8 @@ __device__ __forceinline__ void mfma12(const Frags16 &f, f32x16 (&acc)[2][2])
     for (int mi = 0; mi < 2; ++mi)
 #pragma unroll
         for (int ni = 0; ni < 2; ++ni) {
-            if (!(WG_OPT_2P & 16)) acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.al[mi], f.bh[ni], acc[mi][ni], 0, 0, 0);     // (mfma12 serves the
-            if (!(WG_OPT_2P & 32)) acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.ah[mi], f.bl[ni], acc[mi][ni], 0, 0, 0);     // weight gradients only)
+            acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.al[mi], f.bh[ni], acc[mi][ni], 0, 0, 0);     // (mfma12 serves the
+            acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.ah[mi], f.bl[ni], acc[mi][ni], 0, 0, 0);     // weight gradients only)
             acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.ah[mi], f.bh[ni], acc[mi][ni], 0, 0, 0);
         }
 }
@@ -181,18 +162,13 @@ __device__ __forceinline__ void asm_wait_stage(Stage6 &s)
 {
     asm volatile("s_waitcnt vmcnt(6)" : "+v"(s.ah[0]), "+v"(s.ah[1]), "+v"(s.al[0]), "+v"(s.al[1]), "+v"(s.bh[0]), "+v"(s.bl[0])::"memory");
 }
+// WG_DBG_TRACE (with its selectors WG_DBG_TRACE_SMALL and WGG_TRACE_*) is the one compile-time switch of this library: instrumentation for
+// the trace tools, not a variant of a kernel.  An A/B variant lives on a branch until it is decided.
 #if defined(WG_DBG_TRACE)      // phase timestamps: [workgroup][16]; read back by wg_dbg_trace_read (tools/experiments/conv_trace.py, wgrad_trace.py)
 __device__ unsigned long long wg_dbg_trace[512 * 16];       // 100 MHz wall clock
 __device__ unsigned long long wg_dbg_trace_cyc[512 * 16];   // shader cycles (s_memtime): cycles / wall = the clock the chip holds in the phase
 #endif
-#if defined(WG_DBG_NOBAR)      // timing experiment only (results are garbage): how much of a launch is barrier skew?
-#define WG16W_BAR() do { } while (0)
-#else
 #define WG16W_BAR() __syncthreads()
-#endif
-#if defined(WG_OPT_MFMA32) || defined(WG_OPT_NO_WSPEC) || defined(WG_OPT_DMA)
-#error "the superseded conv kernels (convgemm16w / 16d / 16p) left the tree in round 6: git show 4c099e9:tools/experiments/wg_gemm16_superseded.h"
-#endif
 
 // ------------------------------------------------------------------------------------------------
 // wgrad16s: weight gradients from S-planes.  dW[m][n] = sum_b sum_t A[b][m][t] * B[b][n][t + shift]
@@ -242,12 +218,8 @@ struct WgradSArgs {
 // waits until all sync_n members have done so.  Performance hint only: the wait is bounded, and a workgroup that runs into the bound
 // once (a member that has not been dispatched yet) stops synchronising -- no result depends on the counter, nothing can hang on it.
 #define WG_SYNC_STRIDE 32
-#if !defined(WG_SYNC_EVERY)
 #define WG_SYNC_EVERY 4
-#endif
-#if !defined(WG_SYNC_SPINS)
 #define WG_SYNC_SPINS 256
-#endif
 typedef short s4v __attribute__((ext_vector_type(4)));
 // rows r..r+3 (lo) and r+4..r+7 (hi) of the image, r a multiple of 8 plus the lane's row: the upper four rows are stored rotated
 // by 32 bytes inside the 256-byte row payload (see the staging map of wgrad16s_kernel)
@@ -256,11 +228,7 @@ __device__ __forceinline__ bf16x8 tr_frag(const char *img, int rowoff, int col)
 {
     typedef __attribute__((address_space(3))) s4v *lds_s4p;
     const s4v lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4p)(img + rowoff + col));
-#if defined(WG_OPT_WGRAD_OLDMAP)
-    const s4v hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4p)(img + rowoff + 4 * PITCH + col));
-#else
     const s4v hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4p)(img + rowoff + 4 * PITCH + ((col + 32) & (PITCH - 65))));
-#endif
     bf16x8 r;
     r[0] = lo[0]; r[1] = lo[1]; r[2] = lo[2]; r[3] = lo[3];
     r[4] = hi[0]; r[5] = hi[1]; r[6] = hi[2]; r[7] = hi[3];
@@ -276,7 +244,7 @@ __device__ __forceinline__ int find_sseg_idx(const WgSSeg *s, int n, int blk)
 }
 __device__ __forceinline__ const WgSSeg &find_sseg(const WgSSeg *s, int n, int blk) { return s[find_sseg_idx(s, n, blk)]; }
 
-// MT = 1 (default): 128 x 128 tile, 4 waves, two workgroups per CU.  MT = 2 (-DWG_OPT_WGRAD_TALL): 256 x 128 tile, 8 waves, one
+// MT = 1 (what runs): 128 x 128 tile, 4 waves, two workgroups per CU.  MT = 2 (tried, never launched): 256 x 128 tile, 8 waves, one
 // workgroup per CU; streams 48 KB instead of 64 KB per chunk for the same MFMAs and is still slower (155 vs 137 us).
 // the workgroup's work: tile (bx, by) of the product, split index zs (grouped launches: group * nsplit + split)
 template <int MT>
@@ -313,21 +281,17 @@ __device__ __forceinline__ void wgrad16s_body(const WgradSArgs &a, int bx, int b
     // 256-byte payload -- the transposing fragment read applies the same rotation to its upper four rows (tr_frag) -- which leaves
     // a 2-way write conflict (PMC: a third of this kernel's LDS cycles; profiles/r01m_pmc.json).  It cannot be rotated away: the
     // fragment read needs the four rows of a group on disjoint 16-dword spans of the 64-bank read port, i.e. one rotation per
-    // group, and rows t and t+2 of a group are 32 dwords apart.  The conflict-free 2 x 2 quad map (-DWG_OPT_WGRAD_OLDMAP) is
-    // still 2 % slower end to end: the LDS pipe is half idle here, the global side is what counts.
+    // group, and rows t and t+2 of a group are 32 dwords apart.  tried: the conflict-free 2 x 2 quad map is
+    // still 2 % slower end to end: the LDS pipe is half idle here, the global side is what counts (code: git show
+    // 9da18f4:constant-memory-waveglow_amd/csrc/wg_gemm16s.h).
     const unsigned short *pa[2], *pb[NB];
     size_t la[2], lb_[NB], sba[2], sbb[NB];
     int loffa[2], loffb[NB], roff[NB], pitem[NB];
 #pragma unroll
     for (int j = 0; j < 2; ++j) {                            // A: 32 time steps x 16 MT channel groups = 2 NT units
         const int u = tid + NT * j;
-#if defined(WG_OPT_WGRAD_OLDMAP)    // experiment: the 2 x 2 quad map (32-byte global pieces, no LDS write conflicts, no rotation)
-        const int tl = 2 * (u >> 5) + (u & 1), cg = (u >> 1) & 15;
-        loffa[j] = tl * AROW + cg * 16;
-#else
         const int tl = (u & 7) + 8 * (u / (128 * MT)), cg = (u >> 3) & (16 * MT - 1);
         loffa[j] = tl * AROW + ((cg + 2 * ((tl >> 2) & 1)) & (16 * MT - 1)) * 16;
-#endif
         const int ma = m0 + 8 * cg;
         const int ia = find_sseg_idx(a.sa, a.nseg_a, ma >> 5);
         const WgSSeg &sa = a.sa[ia];
@@ -339,13 +303,8 @@ __device__ __forceinline__ void wgrad16s_body(const WgradSArgs &a, int bx, int b
 #pragma unroll
     for (int j = 0; j < NB; ++j) {                           // B: 32 x 16 = 512 units
         const int u = tid + NT * j;
-#if defined(WG_OPT_WGRAD_OLDMAP)
-        const int tl = 2 * (u >> 5) + (u & 1), cg = (u >> 1) & 15;
-        loffb[j] = tl * WG16_ROWT + cg * 16;
-#else
         const int tl = (u & 7) + 8 * (u >> 7), cg = (u >> 3) & 15;
         loffb[j] = tl * WG16_ROWT + ((cg + 2 * ((tl >> 2) & 1)) & 15) * 16;
-#endif
         const int nb = n0 + 8 * cg;
         const int ib = find_sseg_idx(a.sb, a.nseg_b, nb >> 5);
         const WgSSeg &sb = a.sb[ib];

@@ -35,11 +35,9 @@ struct ConvLayer16hArgs {
     int wo_epi;                // EPI_RESSKIP or EPI_STORE
 };
 
-// WGL_VARIANT (debug A/B builds of the hand-off): 0 = sc1 stores + sc1 loads (default); 1 = + an agent acquire (buffer_inv sc1) behind the
-// poll; 2 = sc0 sc1 (system scope) stores and loads; 3 = plain stores + agent release, agent acquire behind the poll, plain loads
-#if !defined(WGL_VARIANT)
-#define WGL_VARIANT 0
-#endif
+// The hand-off is sc1 stores + sc1 loads.  tried (debug A/B builds): + an agent acquire (buffer_inv sc1) behind the poll; sc0 sc1 (system
+// scope) stores and loads; plain stores + agent release, agent acquire behind the poll, plain loads (code: git show
+// 9da18f4:constant-memory-waveglow_amd/csrc/wg_layer16h.h)
 // A column tile's two counters sit on a 128-byte line of their own: the sets of different column tiles run on different XCDs, whose L2s are
 // not coherent with each other -- counters of two XCDs in one line (the first version: adjacent words) gave lost arrivals and early exits
 // of the poll as soon as the sets were not in lock step (a cold first call), i.e. stale gates
@@ -48,13 +46,7 @@ struct ConvLayer16hArgs {
 template <int OFF>
 __device__ __forceinline__ void wgl_st8_sc1(const unsigned short *base, unsigned voff, const u32x2 &v)
 {
-#if WGL_VARIANT == 2
-    asm volatile("global_store_dwordx2 %0, %1, %2 offset:%3 sc0 sc1" ::"v"(voff), "v"(v), "s"(base), "n"(OFF) : "memory");
-#elif WGL_VARIANT == 3
-    asm volatile("global_store_dwordx2 %0, %1, %2 offset:%3" ::"v"(voff), "v"(v), "s"(base), "n"(OFF) : "memory");
-#else
     asm volatile("global_store_dwordx2 %0, %1, %2 offset:%3 sc1" ::"v"(voff), "v"(v), "s"(base), "n"(OFF) : "memory");
-#endif
 }
 
 // One phase of the layer on the 64 x 64 tile (t0, m0) of plane row b: convgemm16h_body's loop (wg_gemm16h.h) with
@@ -93,8 +85,7 @@ __device__ __forceinline__ void layer16h_phase(const ConvGemm16sArgs &aa, int t0
 #define WGL_LDA(dst, base, voff) asm volatile("global_load_dwordx4 %0, %1, %2" : "=v"(dst) : "v"(voff), "s"(base) : "memory")
 #define WGL_LDB(dst, base, voff)                                                                                           \
     do {                                                                                                                   \
-        if (B_SC1 && WGL_VARIANT == 2) asm volatile("global_load_dwordx4 %0, %1, %2 sc0 sc1" : "=v"(dst) : "v"(voff), "s"(base) : "memory"); \
-        else if (B_SC1 && WGL_VARIANT != 3) asm volatile("global_load_dwordx4 %0, %1, %2 sc1" : "=v"(dst) : "v"(voff), "s"(base) : "memory");       \
+        if (B_SC1) asm volatile("global_load_dwordx4 %0, %1, %2 sc1" : "=v"(dst) : "v"(voff), "s"(base) : "memory");       \
         else asm volatile("global_load_dwordx4 %0, %1, %2" : "=v"(dst) : "v"(voff), "s"(base) : "memory");                 \
     } while (0)
         const unsigned short *zsrc = aa.sseg[0].hi;           // plane position 0 of the first operand: always-zero halo
@@ -156,10 +147,6 @@ __device__ __forceinline__ void layer16h_phase(const ConvGemm16sArgs &aa, int t0
                     ++spins;
                 }
                 *s_bad = spins >= WGL_SPIN_MAX;
-#if WGL_VARIANT == 1 || WGL_VARIANT == 3
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#endif
             }
             __syncthreads();                                  // between the poll and EVERY load of the handed-off bytes
 #pragma unroll
@@ -302,12 +289,6 @@ __global__ __launch_bounds__(512) void convlayer16h_kernel(const ConvLayer16hArg
     if (doA) layer16h_phase<EPI_GATE, true, false>(la.gate, t0, m0, b, smem, nullptr, 0u, nullptr);
     __syncthreads();                                          // every storing wave has drained its stores
     unsigned *arrive = la.sync + (size_t)ct * WGL_SYNC_STRIDE, *depart = arrive + 1;
-#if WGL_VARIANT == 3
-    if (tid == 0 && doA) {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
-#endif
     if (tid == 0 && doA) __hip_atomic_fetch_add(arrive, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     if (!doB) return;
     layer16h_phase<EPIB, false, true>(la.wo, t0, m0, b, smem, arrive, (unsigned)((la.gate.c.M + 63) / 64), &s_bad);

@@ -32,18 +32,13 @@ struct ConvLayer16qArgs {
 };
 
 #define WGLQ_SPIN_MAX (1 << 22)
-// timing bisection only (-DWGLQ_DBG=<mask>; results are WRONG with any bit): 1 plain B loads, 2 plain gate stores, 4 no R tiles, 8 no poll
-#if !defined(WGLQ_DBG)
-#define WGLQ_DBG 0
-#endif
 
 // EPI_GATE_SO's column block (wgq_gate_nb, wg_gemm16q.h) with the gate's S-plane stored write-through; the saved tanh / sigmoid planes
 // (private to this workgroup's later gate backward) keep their non-temporal stores
 template <int OFF>
 __device__ __forceinline__ void wglq_st8_sc1(const unsigned short *base, unsigned voff, const u32x2 &v)
 {
-    if (WGLQ_DBG & 2) asm volatile("global_store_dwordx2 %0, %1, %2 offset:%3" ::"v"(voff), "v"(v), "s"(base), "n"(OFF) : "memory");
-    else asm volatile("global_store_dwordx2 %0, %1, %2 offset:%3 sc1" ::"v"(voff), "v"(v), "s"(base), "n"(OFF) : "memory");
+    asm volatile("global_store_dwordx2 %0, %1, %2 offset:%3 sc1" ::"v"(voff), "v"(v), "s"(base), "n"(OFF) : "memory");
 }
 template <int NB, int NBI>
 __device__ __forceinline__ void wglq_gate_nb(f32x4 (&acc)[4][NB], bool live, const float *const (&bt)[2], const float *const (&bs)[2],
@@ -134,7 +129,7 @@ __global__ __launch_bounds__(1024) void convlayer16q_kernel(const ConvLayer16qAr
         ty = q % ag.nty; tz = q / ag.nty;
     };
     const int my_e = xslot & 1;                               // this workgroup's row-tile index (nty == 2, xslots even): the same in every round
-    auto owns = [&](int k) { return !(WGLQ_DBG & 4) && my_e == ((k < mine - 1 ? k : mine - 2) & 1); };
+    auto owns = [&](int k) { return my_e == ((k < mine - 1 ? k : mine - 2) & 1); };
     // item p of this workgroup's list -> (kind, round):  G_0; for k = 1 .. n-1: G_k, [R_{k-1}]; [R_{n-1}]
     struct Item { int kind, k; };
     int nitems = 0, total = 0;
@@ -183,15 +178,11 @@ __global__ __launch_bounds__(1024) void convlayer16q_kernel(const ConvLayer16qAr
         const int b_off = wg16q_off(bt, cg0);
         const unsigned voff_b = (unsigned)((cg0 * g.P + bt) * 16);
 #define WGLQ_LD(dst, base, voff) asm volatile("global_load_dwordx4 %0, %1, %2" : "=v"(dst) : "v"(voff), "s"(base) : "memory")
-#define WGLQ_LDS1(dst, base, voff)                                                                                          \
-    do {                                                                                                                   \
-        if (WGLQ_DBG & 1) asm volatile("global_load_dwordx4 %0, %1, %2" : "=v"(dst) : "v"(voff), "s"(base) : "memory");     \
-        else asm volatile("global_load_dwordx4 %0, %1, %2 sc1" : "=v"(dst) : "v"(voff), "s"(base) : "memory");              \
-    } while (0)
+#define WGLQ_LDS1(dst, base, voff) asm volatile("global_load_dwordx4 %0, %1, %2 sc1" : "=v"(dst) : "v"(voff), "s"(base) : "memory")
         const unsigned short *zsrc = ag.sseg[0].hi;           // plane position 0 of the gate conv's first operand: always-zero halo
         auto issue = [&](Stage &st) {                         // exactly 6 loads in straight-line code (tools/check_asm_loads.py)
             const bool live = gchunk < total;
-            if (live && v == 0 && it.kind && !(WGLQ_DBG & 8)) {
+            if (live && v == 0 && it.kind) {
                 // an R tile's first chunk: the column tile's two G tiles must have been published (every loader wave polls for itself;
                 // bounded: a hand-off that never comes shows as NaN outputs, not as a hang)
                 const unsigned *arrive = la.sync + (size_t)ct * WGL_SYNC_STRIDE;

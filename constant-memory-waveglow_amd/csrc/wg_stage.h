@@ -94,19 +94,7 @@ __global__ __launch_bounds__(WGS_THREADS) void wf_rowsteps_kernel(const WgStage 
             const WgStage &st = *reinterpret_cast<const WgStage *>(s_stage);
             const int kind = __builtin_amdgcn_readfirstlane(st.kind), nb = __builtin_amdgcn_readfirstlane(st.nblocks);
             for (int blk = (int)blockIdx.x; blk < nb; blk += (int)G) {
-#if defined(WG_DBG_ROWWALK_ONLY)   // bisecting aid: only this stage of row 0 runs
-                if (s != WG_DBG_ROWWALK_ONLY || row != 0) continue;
-#endif
-#if defined(WG_DBG_ROWWALK)    // bisecting aid: bit 0 skips the conv stages, bit 1 the S-plane conversion, bit 2 the coupling
-                if (((WG_DBG_ROWWALK & 1) && kind <= WGS_CONV_RESSKIP) || ((WG_DBG_ROWWALK & 2) && kind == WGS_TOSPLANE) ||
-                    ((WG_DBG_ROWWALK & 4) && kind == WGS_WFCOUPLE) || ((WG_DBG_ROWWALK & 8) && kind == WGS_CONV_STORE) ||
-                    ((WG_DBG_ROWWALK & 16) && kind == WGS_CONV_GATE) || ((WG_DBG_ROWWALK & 32) && kind == WGS_CONV_RESSKIP)) continue;
-#endif
-#if defined(WG_DBG_ROWWALK_GLOBALARGS)
-                const ConvGemm16sArgs &cv = prog[s].u.conv;
-#else
                 const ConvGemm16sArgs &cv = st.u.conv;
-#endif
                 if (kind == WGS_CONV_STORE) convgemm16h_body<EPI_STORE, true>(cv, blk, row + 1, smem);
                 else if (kind == WGS_CONV_GATE) convgemm16h_body<EPI_GATE, true>(cv, blk, row + 1, smem);
                 else if (kind == WGS_CONV_RESSKIP) convgemm16h_body<EPI_RESSKIP, true>(cv, blk, row + 1, smem);

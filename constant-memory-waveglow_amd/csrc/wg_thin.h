@@ -23,9 +23,6 @@
 #define WGTH_BATCH 8                // start: channel groups (2 x 16 bytes per lane each) a wave has in flight
 #define WGTH_BATCH2 16              // end: 4-row groups (16 bytes per lane each) a wave has in flight
 
-#if !defined(WGTH_DBG)
-#define WGTH_DBG 0                  // timing bisection only: 1 no reduction, 2 no weight-gradient walk, 4 no tile / data-gradient work, 8 no loads
-#endif
 // out[e] = sum_p part[p][e] (np partials of n floats, n a multiple of 32): a block takes 8 columns of 16 bytes, thread (column, lane l of 32)
 // adds partials l, l + 32, ... (all its loads in flight), thread (column, 0) then adds the 32 lanes' sums in lane order -- a fixed order,
 // so the result is reproducible.  (Folding inside the producing launch -- the last workgroup to finish, found by an atomic ticket, one
@@ -103,7 +100,7 @@ __global__ __launch_bounds__(WGTH_THREADS) void thin_start_kernel(const ThinStar
             for (int q = 0; q < WGTH_BATCH; ++q) {
                 const int cg = cg0 + 4 * q;
                 h[q] = u32x4{0u, 0u, 0u, 0u}; l[q] = h[q];
-                if (live && cg < ncg && !(WGTH_DBG & 8)) {
+                if (live && cg < ncg) {
                     const size_t i = s_index(a.dh, g, b, cg * 8, t);
                     h[q] = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(a.dh.hi + i));
                     l[q] = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(a.dh.hi + a.dh.lo_off + i));
@@ -112,7 +109,7 @@ __global__ __launch_bounds__(WGTH_THREADS) void thin_start_kernel(const ThinStar
 #pragma unroll
             for (int q = 0; q < WGTH_BATCH; ++q) {
                 const int cg = cg0 + 4 * q;
-                if (cg < ncg && !(WGTH_DBG & 4)) {
+                if (cg < ncg) {
                     float v[8];
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
@@ -147,7 +144,7 @@ __global__ __launch_bounds__(WGTH_THREADS) void thin_start_kernel(const ThinStar
 #pragma unroll
         for (int r = 0; r < WGTH_MAXROWS; ++r) {
             const int c = tid + r * WGTH_THREADS;
-            if (c < a.C && !(WGTH_DBG & 2)) {
+            if (c < a.C) {
                 const float *row = tile + (size_t)c * WGTH_LDT;
 #pragma unroll 8
                 for (int tt = 0; tt < WGTH_TB; ++tt) {
@@ -219,12 +216,12 @@ __global__ __launch_bounds__(WGTH_THREADS) void thin_end_kernel(const ThinEndArg
                 for (int q = 0; q < WGTH_BATCH2; ++q) {
                     const int m = mb + 16 * q + r4;
                     v[q] = f32x4{0.f, 0.f, 0.f, 0.f};
-                    if (m < a.Cs && !(WGTH_DBG & 8)) v[q] = __builtin_nontemporal_load(reinterpret_cast<const f32x4 *>(paddr(a.skip, g, b, m, t0 + q4)));
+                    if (m < a.Cs) v[q] = __builtin_nontemporal_load(reinterpret_cast<const f32x4 *>(paddr(a.skip, g, b, m, t0 + q4)));
                 }
 #pragma unroll
                 for (int q = 0; q < WGTH_BATCH2; ++q) {
                     const int m = mb + 16 * q + r4;
-                    if (m < a.Cs && !(WGTH_DBG & 4)) {
+                    if (m < a.Cs) {
                         float *dst = tile + (size_t)m * WGTH_LDT + q4;
                         dst[0] = t0 + q4 + 0 < g.T ? v[q][0] : 0.f; dst[1] = t0 + q4 + 1 < g.T ? v[q][1] : 0.f;
                         dst[2] = t0 + q4 + 2 < g.T ? v[q][2] : 0.f; dst[3] = t0 + q4 + 3 < g.T ? v[q][3] : 0.f;
@@ -237,7 +234,7 @@ __global__ __launch_bounds__(WGTH_THREADS) void thin_end_kernel(const ThinEndArg
 #pragma unroll
             for (int k = 0; k < K2P; ++k) gs[tl * K2P + k] = gk[k];
         }
-        for (int cg = wv; cg < ncg && !(WGTH_DBG & 4); cg += 4) {
+        for (int cg = wv; cg < ncg; cg += 4) {
             float v[8];
 #pragma unroll
             for (int e = 0; e < 8; ++e) v[e] = 0.f;
@@ -265,7 +262,7 @@ __global__ __launch_bounds__(WGTH_THREADS) void thin_end_kernel(const ThinEndArg
 #pragma unroll
         for (int r = 0; r < WGTH_MAXROWS; ++r) {
             const int m = tid + r * WGTH_THREADS;
-            if (m < a.Cs && !(WGTH_DBG & 2)) {
+            if (m < a.Cs) {
                 const float *row = tile + (size_t)m * WGTH_LDT;
 #pragma unroll 8
                 for (int tt = 0; tt < WGTH_TB; ++tt) {

@@ -39,13 +39,9 @@
 #include <type_traits>
 
 #define WGT_PH_MAX 8
-#if !defined(WGT_POLL_SLEEP)
 #define WGT_POLL_SLEEP 2                                   // the loaders look at the compute waves' progress every 64 x this many cycles
-#endif
 #define WGT_SPIN_CAP (1 << 22)                             // polls of a hand-over word before a wave gives up (about a second) and the result is poisoned
-#if !defined(WGT_BAR_GROUP)
 #define WGT_BAR_GROUP 3                                    // the chunk's barrier sits in front of this MFMA group
-#endif
 #define WGT_IMG (32 * 256)                                 // one [32 t][128 c] bf16 image
 #define WGT_BUF (6 * WGT_IMG)                              // A: 2 row halves x (hi, lo); B: hi, lo  = 48 KB
 struct WgtPhase {
@@ -100,10 +96,6 @@ typedef __attribute__((address_space(3))) s4v *wgt_lds_s4p;
 // one MFMA operand (8 consecutive time steps of the lane's channel): two 4 x 16 transposing reads
 __device__ __forceinline__ bf16x8 wgt_frag(const char *p1, const char *p2)
 {
-#if defined(WG_DBG_B128READ)   // timing experiment only (garbage results): one 16-byte read per fragment instead of two transposing 8-byte reads
-    (void)p2;
-    return *reinterpret_cast<const bf16x8 *>((const char *)((size_t)p1 & ~(size_t)15));
-#endif
     const s4v lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((wgt_lds_s4p)p1);
     const s4v hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((wgt_lds_s4p)p2);
     bf16x8 r;
@@ -177,9 +169,6 @@ __global__ __launch_bounds__(768) void wgrad16t_kernel(const WgtArgs aa_by_value
         // gone (profiles/r03c_wgrad_phases.txt).  So the addresses are SCALAR: a wave fetches, per unit, 2 channel groups x 32 time steps
         // = 16 channels of one 32-channel block, which lie in ONE operand segment; its source is an SGPR pointer that the scalar unit
         // advances chunk by chunk, plus one 32-bit lane offset that never changes.
-#if defined(WG_DBG_NOLOADER)   // timing experiment only: the compute waves alone (with their barriers)
-        return;
-#endif
         const int lw = wave - 8;
         const int tl = lane & 31, half = lane >> 5;           // this lane's time step inside a chunk; which of the wave's two channel groups
         const unsigned voff = (unsigned)((half * gP + tl) * 16);
@@ -243,11 +232,7 @@ __global__ __launch_bounds__(768) void wgrad16t_kernel(const WgtArgs aa_by_value
             }
         };
         setup(0);
-#if defined(WG_DBG_NOLOAD)     // timing experiment only: the loaders write whatever their staging registers hold
-#define WGT_LDP(dst, base, vo) asm volatile("" : "=v"(dst) : "v"(vo), "s"(base))
-#else
 #define WGT_LDP(dst, base, vo) asm volatile("global_load_dwordx4 %0, %1, %2" : "=v"(dst) : "v"(vo), "s"(base) : "memory")
-#endif
         // exactly twelve loads in straight-line code (tools/check_asm_loads.py): units without a source and chunks past the end read the
         // zero halo (selected base, lane offset 0), no branch between a load and its wait
         auto issue = [&](WgtStage &st) {
@@ -272,9 +257,6 @@ __global__ __launch_bounds__(768) void wgrad16t_kernel(const WgtArgs aa_by_value
         };
 #undef WGT_LDP
         auto write = [&](const WgtStage &st, int buf) {
-#if defined(WG_DBG_NOWRITE)    // timing experiment only
-            return;
-#endif
             char *sb = smem + buf * WGT_BUF;
 #pragma unroll
             for (int u = 0; u < 6; ++u) {
@@ -336,12 +318,6 @@ __global__ __launch_bounds__(768) void wgrad16t_kernel(const WgtArgs aa_by_value
         return;
     }
     // ------------------------------- compute waves: 4 (M) x 2 (N), a 64 x 64 tile each -------------------------------
-#if defined(WG_DBG_HALFWAVES)  // timing experiment only: ONE compute wave per SIMD (how fast is a wave's instruction stream alone?)
-    if (wave >= 4) return;
-#endif
-#if defined(WGT_COMPUTE_PRIO)
-    __builtin_amdgcn_s_setprio(WGT_COMPUTE_PRIO);            // experiment: the compute waves' instructions ahead of the loaders'
-#endif
     const int wm = wave >> 1, wc = wave & 1;
     const int fg = lane >> 4, fq = (lane & 15) >> 2, fp = lane & 3;
     const int t1 = 8 * fg + fq, t2 = t1 + 4;
@@ -351,11 +327,7 @@ __global__ __launch_bounds__(768) void wgrad16t_kernel(const WgtArgs aa_by_value
     const int ao2 = (wm >> 1) * WGT_IMG + wgt_off(t2, 8 * (wm & 1) + (fp >> 1)) + 8 * (fp & 1);
     const int bo1 = 4 * WGT_IMG + wgt_off(t1, 8 * wc + (fp >> 1)) + 8 * (fp & 1);
     const int bo2 = 4 * WGT_IMG + wgt_off(t2, 8 * wc + (fp >> 1)) + 8 * (fp & 1);
-#if defined(WGT_NO_SB)         // experiment: the compiler's own order of the chunk loop
-#define WGT_SB() do { } while (0)
-#else
 #define WGT_SB() __builtin_amdgcn_sched_barrier(0)
-#endif
 #if defined(WG_DBG_TRACE)      // phase stamps (slots 8..15 of the conv kernels' trace arrays): start, first barrier, then per item main loop / slab done
 #define WGT_TRACE(slot) do { if (lane == 0 && wave == 0 && (slot) < 8) { \
         wg_dbg_trace[blockIdx.x * 16 + 8 + (slot)] = wall_clock64(); wg_dbg_trace_cyc[blockIdx.x * 16 + 8 + (slot)] = clock64(); } } while (0)
@@ -374,9 +346,6 @@ __global__ __launch_bounds__(768) void wgrad16t_kernel(const WgtArgs aa_by_value
     // fragment is re-fetched from the next chunk as soon as its last MFMAs are issued (convgemm16q_kernel's register budget: a second
     // set of A fragments, fetched a whole chunk ahead, spilled at three waves per SIMD).
     auto wait_ready = [&](unsigned want) {                   // all four loader waves have staged chunk want - 1
-#if defined(WG_DBG_NOLOADER) || defined(WG_DBG_NOWAITREADY)
-        return;
-#endif
         for (int spins = 0;;) {
             const unsigned v = __hip_atomic_load(&s_ready[lane & 3], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
             const unsigned m = min(min((unsigned)__builtin_amdgcn_readlane(v, 0), (unsigned)__builtin_amdgcn_readlane(v, 1)),
@@ -394,22 +363,16 @@ __global__ __launch_bounds__(768) void wgrad16t_kernel(const WgtArgs aa_by_value
 #pragma unroll
         for (int nb = 0; nb < 4; ++nb) {
             const int cb = nb & 1, nx = cb ^ 1;
-#if !defined(WG_DBG_NOHANDOVER)
             if (nb == 3 && gc + 1 < total) {
                 WGT_SB();
                 wait_ready((unsigned)(gc + 2));          // the next chunk is in LDS (it normally has been for a while)
             }
-#endif
             WGT_SB();
 #pragma unroll
             for (int mb = 0; mb < 4; ++mb) {
-#if defined(WG_DBG_NOMFMA)     // timing experiment only: fragments are fetched, nothing is multiplied
-                if (false) {
-#else
                 if (FULL || nb < nbv) {
-#endif
-                    if (!(WG_OPT_2P & 16)) acc[mb][nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al[mb], bh[cb], acc[mb][nb], 0, 0, 0);
-                    if (!(WG_OPT_2P & 32)) acc[mb][nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[mb], bl[cb], acc[mb][nb], 0, 0, 0);
+                    acc[mb][nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al[mb], bh[cb], acc[mb][nb], 0, 0, 0);
+                    acc[mb][nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[mb], bl[cb], acc[mb][nb], 0, 0, 0);
                     acc[mb][nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[mb], bh[cb], acc[mb][nb], 0, 0, 0);
                 }
                 // the next group's B fragments in two halves behind the first and the second row block's MFMAs: fewer LDS instructions in a
@@ -422,12 +385,10 @@ __global__ __launch_bounds__(768) void wgrad16t_kernel(const WgtArgs aa_by_value
                 if (mb == 1) {
                     WGT_SB();
                     bl[nx] = nb == 3 ? rdB(nxt, 0, 1) : rdB(cur, nb + 1, 1);
-#if !defined(WG_DBG_NOHANDOVER)
                     if (nb == 2) {
                         WGT_ORDER();
                         __hip_atomic_store(&s_done[wave], (unsigned)(gc + 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
                     }
-#endif
                     WGT_SB();
                 }
                 if (nb == 3) {

@@ -187,57 +187,36 @@ struct WnD {
 
 // skip = sum_i Wskip_i gate_i as one product at the end of the WN (all gates kept) instead of a read-modify-write of the skip plane
 // per layer: the residual convs are bound by their HBM bytes, this takes a third of them away
-#if !defined(WG_FUSED_SKIP_MIN_COLS)
 #define WG_FUSED_SKIP_MIN_COLS 4096
-#endif
 // The residual stream h_i and its gradient dh_i exist as S-planes ONLY (hi + lo bf16, ~16 significant bits) in the S-plane mode: the
 // fp32 copies were written and read back by every residual / data-gradient conv just to carry the running sum, a quarter of those
 // launches' HBM bytes.  The contractions read h and dh from the S-planes either way; what changes is that the rounding to hi + lo
 // (2^-17 relative) now accumulates along the 8 layers of a WN instead of being refreshed from an exact fp32 chain.
 inline bool s_only_chain(const Ctx &cx, const WnD &d)
 {
-#if !defined(WG_OPT_NO_S_ONLY)
-#if defined(WG_OPT_S_ONLY_1D)                               // A/B build: WN2D keeps its fp32 residual planes (before round 6's last commits)
-    return cx.prec == 2 && !d.mode2d;
-#else
     // (WN2D since the end of round 6 -- its 64-row products read the accumulate-into S-plane like every other form of convgemm16q: WaveFlow's
     // step 39.4 -> 36.6 ms on one box, residual conv 43 -> 31 us, data-gradient conv 131 -> 119 us; not inside the row-by-row inverse, whose
     // recorded stages keep the planes they were built and tested with)
     return cx.prec == 2 && (!d.mode2d || (!cx.rec && !cx.row_sel1));      // measured (1-D): step 78.8 -> 75.8 ms; errors against the oracle unchanged
-#endif
-#else                                                       // (tools/experiments/err_report.py: z 3.8e-6, worst gradient 8.9e-6 of its max)
-    (void)cx; (void)d; return false;
-#endif
+                                                                          // (tools/experiments/err_report.py: z 3.8e-6, worst gradient 8.9e-6 of its max)
 }
 // Weight gradients of all layers of a WN in ONE grouped launch after its layer loop (WgradGrp, wg_gemm16s.h) instead of two launches
 // per layer.  Needs every layer's gate gradient (the 1-D WN keeps them anyway for the one-product conditioning gradient, fused_dy)
 // and every layer's dh, each as its own S-plane: + (depth - 1) planes of 2 Cd and of C channels.
 inline bool grouped_wgrad(int prec, const WnD &d)
 {
-#if defined(WG_OPT_NO_WGRAD_GROUP)
-    (void)prec; (void)d; return false;
-#else
     return prec == 2 && d.depth >= 2 && d.depth <= WG_GRP_MAX && d.radix + 1 + (d.bias ? 1 : 0) <= WG_MAX_SEG;
-#endif
 }
 inline bool fused_skip(const WnD &d)
 {
-#if defined(WG_OPT_NO_FUSED_SKIP)
-    (void)d; return false;
-#else
     return d.depth + (d.bias ? 1 : 0) <= WG_MAX_SEG;
-#endif
 }
 
 // dy = sum_i V_i^T dxy_i as one product after the layer loop (every layer's dxy kept: +(depth - 1) x 2 Cd planes of workspace) instead of
 // an HBM-bound launch and a read-modify-write of dy per layer; 1-D WN only (WaveFlow sums dxy over the height axis first)
 inline bool fused_dy(const WnD &d)
 {
-#if defined(WG_OPT_NO_FUSED_DY)
-    (void)d; return false;
-#else
     return d.depth <= WG_MAX_SEG && !d.mode2d;
-#endif
 }
 
 
@@ -246,31 +225,19 @@ inline bool fused_dy(const WnD &d)
 // gate conv of a recompute pass 4 bytes per element less to write: 49 of the ~200 MB a layer launch stores at the training shape.
 inline bool tw_from_gate(const Ctx &cx)
 {
-#if WG_TS_INTERLEAVED && !defined(WG_OPT_KEEP_TANH)
     return cx.prec == 2 && env_sw().tw_from_gate;
-#else
-    (void)cx; return false;
-#endif
 }
 // The skip sum S = sum_l Wskip_l gate_l and its gradient dS = W_end^T G never formed (Weff_l = W_end Wskip_l, wg_small.h weff_kernel):
 // S-plane mode, 1-D WN without biases (a skip bias would enter `out` through W_end as well), every layer's gate kept (fused_skip).
 inline bool lowrank_shape(const WnD &d)
 {
-#if defined(WG_OPT_NO_LOWRANK)
-    (void)d; return false;
-#else
     return d.prec == 2 && !d.bias && fused_skip(d) && d.Cd % 64 == 0 && 2 * d.ic * d.Cs <= 8192 && (!d.mode2d || d.ic == 1);                           // (W_end in weff_kernel's LDS)
-#endif
 }
 
 // ... and the gate convs leave their share of `out` themselves (ConvGemm16sArgs::part): 8 floats per column and (row tile, wave row)
 inline bool gate_parts_shape(const WnD &d)
 {
-#if defined(WG_OPT_NO_GATE_PARTS)
-    (void)d; return false;
-#else
     return lowrank_shape(d) && 2 * d.ic <= 8 && (2 * d.Cd) % 64 == 0 && (size_t)(d.Cd / 32) * 1024 <= 8192;
-#endif
 }
 inline int gate_part_slots(const WnD &d) { return 2 * d.Cd / 64; }      // one per 32 gate channels = per wave row of a gate conv
 inline int gate_part_prow(const WnD &d) { return 2 * d.ic <= 2 ? 2 : 8; }   // floats per partial row (2: WaveFlow's WN2D, the 16x16x32 kernels' epilogue only)
@@ -281,11 +248,7 @@ inline int gate_part_prow(const WnD &d) { return 2 * d.ic <= 2 ? 2 : 8; }   // f
 inline bool wn_pack_fused_shape(const WnD &d);
 inline bool start_fold_shape(const WnD &d)
 {
-#if defined(WG_OPT_NO_START_FOLD)
-    (void)d; return false;
-#else
     return d.prec == 2 && !d.bias && d.ic <= 16 && d.depth >= 2 && wn_pack_fused_shape(d);
-#endif
 }
 
 Geo make_geo(int B, int T, int halo_need)
@@ -393,11 +356,7 @@ inline bool wn_pack_fused(const WnD &d);
 inline bool wn_pack_fused_shape(const WnD &d) { return wn_pack_fused(d); }
 inline bool wn_pack_fused(const WnD &d)
 {
-#if defined(WG_OPT_NO_PACK_FUSE)
-    (void)d; return false;
-#else
     return !d.bias;
-#endif
 }
 struct JobBatch {
     Ctx *ctx;
@@ -776,9 +735,6 @@ struct WgtPlan {
 static WgtPlan plan_wgt(int tm0, int tn0, int tm1, int tn1, int ng, int K)
 {
     WgtPlan pl;
-#if defined(WG_OPT_NO_WGRAD16T)
-    return pl;
-#endif
     const int T0 = tm0 * tn0, T1 = tm1 * tn1;
     if (T0 < 1 || T1 < 1 || T0 > 32 || T1 > 32 || ng < 1 || K < 1) return pl;
     auto sets_per_xcd = [&](int room, int T) {               // most sets of T tiles in `room` slots whose total over 8 XCDs is a multiple of ng
@@ -825,9 +781,6 @@ static WgtPlan plan_wgt(int tm0, int tn0, int tm1, int tn1, int ng, int K)
 static WgtPlan plan_wgt_rounds(int tm0, int tn0, int tm1, int tn1, int ng, int K)
 {
     WgtPlan best;
-#if defined(WG_OPT_NO_WGRAD16T) || defined(WG_OPT_NO_WGT_ROUNDS)
-    return best;
-#endif
     const int T1 = tm1 * tn1;
     if (tm0 < 1 || tn0 < 1 || T1 < 1 || T1 > 32 || tm0 > 32 || ng < 1 || K < 1) return best;
     const long work = ((long)tm0 * tn0 + T1) * ng * K;
@@ -1200,14 +1153,12 @@ static ConvRoute conv_args(const Ctx &cx, const ConvOp &op)
     as.img_stride = (size_t)op.chunks() * op.lda * WG16_BK;
     if (cx.prec == 1) return rt;
     const SegSpec *segs = op.seg;
-#if !defined(WG_OPT_NO_TAP_IL)
     {   // leading segments that are taps of one plane: walked interleaved (ConvGemm16sArgs::tap_il)
         int nt = 1;
         while (nt < op.nseg && segs[nt].s == segs[0].s && segs[nt].nch == segs[0].nch && segs[nt].sCp == segs[0].sCp &&
                segs[nt].sch0 == segs[0].sch0 && segs[nt].per_item == segs[0].per_item) ++nt;
         if (nt >= 2 && segs[0].s && segs[0].nch % WG16_BK == 0) { as.tap_il = nt; as.tap_chunks = segs[0].nch / WG16_BK; }
     }
-#endif
     as.s0 = op.s0; as.saux = op.saux; as.prow = op.prow;
     if (op.epi == EPI_GATE && op.part && (size_t)(op.M / 64) * 1024 <= WGG_EFF_BYTES) { as.eff = op.eff; as.part = op.part; }
     for (int s = 0; s < op.nseg; ++s) {
@@ -1222,21 +1173,7 @@ static ConvRoute conv_args(const Ctx &cx, const ConvOp &op)
 }
 
 // fewer 128 x 128 tiles than 3/4 of the workgroup slots: the S-plane kernels take 128 x 64 tiles
-static bool conv_small(const ConvOp &op, const dim3 &grid)
-{
-    bool small = grid.x * grid.y * grid.z < 384;
-#if defined(WG_OPT_NI1_MASK)                      // experiment: 128 x 64 tiles (twice the tiles: a fuller last round) for a class of launches
-    const int epi = op.epi;
-    const long long Ksum = op.ksum();
-    if ((WG_OPT_NI1_MASK & 1) && epi == EPI_STORE && Ksum <= 256) small = true;
-    if ((WG_OPT_NI1_MASK & 2) && epi == EPI_DGATE) small = true;
-    if ((WG_OPT_NI1_MASK & 4) && epi == EPI_STORE && Ksum >= 1024 && Ksum < 2048) small = true;
-    if ((WG_OPT_NI1_MASK & 8) && epi == EPI_STORE && Ksum >= 2048) small = true;
-#else
-    (void)op;
-#endif
-    return small;
-}
+static bool conv_small(const dim3 &grid) { return grid.x * grid.y * grid.z < 384; }
 
 // Which kernel, tiles and grid a conv product takes.  Launches nothing and changes nothing, so that whoever needs the decision without
 // the launch (gate_parts_on) gets it from the same rules as launch_conv.
@@ -1259,30 +1196,20 @@ ConvRoute route_conv(const Ctx &cx, const ConvOp &op)
         return pick(CK_16, epi, grid, 256);
     }
     // persistent launch: one workgroup per resident slot (two per CU), each walking its share of the tile grid -- see the
-    // kernel; the gate backward stays at one workgroup per tile.  -DWG_OPT_NO_PERSIST: one workgroup per tile everywhere.
+    // kernel; the gate backward stays at one workgroup per tile.
     const int cus = device_cus();
-    const bool small = conv_small(op, grid);
+    const bool small = conv_small(grid);
     as.ntx = small ? (int)grid.x * 2 : (int)grid.x; as.nty = (int)grid.y; as.ntz = (int)grid.z;
     const int ntiles = as.ntx * as.nty * as.ntz;
-    int slots = epi == EPI_DGATE ? ntiles : 2 * cus;
-#if defined(WG_OPT_NO_PERSIST)
-    slots = ntiles;
-#endif
+    const int slots = epi == EPI_DGATE ? ntiles : 2 * cus;
     const dim3 gp = epi == EPI_DGATE ? dim3(as.ntx, as.nty, as.ntz) : dim3(std::min(ntiles, slots));
     // plane rows dealt to XCDs (ConvGemm16sArgs::xcd_items): full persistent grids whose plane rows divide by the 8 XCDs
-    const bool xcd_rows = epi != EPI_DGATE && as.ntz % 8 == 0 && g.rows == 0
-#if defined(WG_OPT_NO_XCD_ROWS)
-                          && false
-#endif
-        ;
+    const bool xcd_rows = epi != EPI_DGATE && as.ntz % 8 == 0 && g.rows == 0;
     if (xcd_rows && ntiles >= slots && slots % 8 == 0) as.xcd_items = as.ntz / 8;
-#if !defined(WG_OPT_NO_XCD_COLS)
     // XCD columns (ConvGemm16sArgs::xcd_items < 0): full persistent grids whose plane rows do NOT divide by the 8 XCDs
     // (measured, WSRGlow at batch 12: the conditioning gradient -- 29 row tiles -- 516.9 -> 478.6 us; launches with few row tiles do not
     // gain -- the gate conv, 4 row tiles: 107.6 -> 109.3 us -- so the order is used from 8 row tiles on)
     else if (epi != EPI_DGATE && g.rows == 0 && !cx.row_sel1 && ntiles >= slots && slots % 8 == 0 && as.ntx * as.ntz >= 8 && as.nty >= 8) as.xcd_items = -1;
-#endif
-#if !defined(WG_OPT_NO_HTILE)
     // at most half as many 128 x 64 tiles as CUs (one utterance being synthesised, WaveFlow's row-by-row inverse): such a launch
     // is as long as its slowest CU needs to take in its operands -- 64 x 64 tiles, twice the workgroups (wg_gemm16h.h)
     // (measured and not adopted: also where the 128 x 64 tiles are 1 - 1.5 per CU -- WSRGlow's gate conv, 384 such tiles --
@@ -1295,18 +1222,14 @@ ConvRoute route_conv(const Ctx &cx, const ConvOp &op)
         as.nty = 2 * (int)grid.y;
         return pick(CK_H, epi, dim3(as.ntx * as.nty * as.ntz), 512);
     }
-#endif
     // the instantiations with hand-issued epilogues: S-plane-only stores (no fp32 output, no fp32 accumulate-into plane), the S-plane-only
     // gate and gate backward, and stores to an fp32 plane only
     int te = epi;
-#if !defined(WG_OPT_NO_EPI_BATCH)
     if (epi == EPI_STORE && as.s0.hi && !a.out0.p && !a.aux0.p) te = EPI_STORE_SO;
-    else if (epi == EPI_GATE && as.s0.hi && !a.out0.p && WG_TS_INTERLEAVED) te = EPI_GATE_SO;
-    else if (epi == EPI_DGATE && as.s0.hi && !a.out0.p && WG_TS_INTERLEAVED) te = EPI_DGATE_SO;
+    else if (epi == EPI_GATE && as.s0.hi && !a.out0.p) te = EPI_GATE_SO;
+    else if (epi == EPI_DGATE && as.s0.hi && !a.out0.p) te = EPI_DGATE_SO;
     else if (epi == EPI_STORE && !as.s0.hi && a.out0.p && !as.saux.hi) te = EPI_STORE_FO;
-#endif
     const bool so_gate = te == EPI_GATE_SO;
-#if !defined(WG_OPT_NO_G192)
     // 256 x 192 tiles over flattened columns, eight multiplying waves fed by LDS-DMA (wg_gemm16g.h): the S-plane-only gate conv and
     // store / data-gradient / skip products whose tiles deal out evenly over the CUs (env WG_G192=0 restores the 256 x 128 / 128 x 128 forms)
     // (products of fewer than 16 chunks -- the residual conv, K = 256: 36.6 against 35.3 us -- stay on the older kernel: a tile that
@@ -1339,14 +1262,10 @@ ConvRoute route_conv(const Ctx &cx, const ConvOp &op)
             return pick(CK_G, te, dim3(cus), 512);
         }
     }
-#endif
-#if !defined(WG_OPT_NO_M64)
     // products with at most 64 rows on 64 x 128 tiles (convgemm16q_kernel<.., M64>): WaveFlow's 64-channel WN2D -- on 128-row tiles
     // half of every MFMA multiplied padding (the data-gradient conv: 181 TF against 314 for the full-height gate conv)
     if (!small && M <= 64 && epi != EPI_GATE && epi != EPI_RESSKIP) return pick(CK_Q_M64, te, gp, 512);
-#endif
     if (small) return pick(CK_Q1, te, gp, 512);
-#if !defined(WG_OPT_NO_CG2)
     // products with ONE 128-row tile (WaveFlow's gate conv, M = 2 Cd = 128) on 128 x 256 tiles: one 16-wave workgroup per CU whose two
     // compute groups share the A image of every chunk (convgemm16q_kernel<.., CG2>) -- 25 % less L2 -> LDS traffic for a launch
     // that sits at the per-CU intake limit
@@ -1357,8 +1276,6 @@ ConvRoute route_conv(const Ctx &cx, const ConvOp &op)
             return pick(CK_Q_CG2, te, dim3(std::min(nt2, cus)), 1024);
         }
     }
-#endif
-#if !defined(WG_OPT_NO_MG2)
     // 256 x 128 tiles, one 16-wave workgroup per CU (the compute groups share every chunk's B image: 25 % less L2 -> LDS
     // traffic, no slower co-resident workgroup left to finish alone): gate conv 125.7 -> 118.6 us.  Only where the tiles deal out
     // evenly over the CUs: at 1.5 tiles per CU (the 256-row products of the training shape: 384 such tiles) the half-empty second
@@ -1371,7 +1288,6 @@ ConvRoute route_conv(const Ctx &cx, const ConvOp &op)
         if (cus % 8) as.xcd_items = 0;                // (mg2_ok: at least one tile per CU)
         return pick(CK_Q_MG2, te, dim3(std::min(ntiles / 2, cus)), 1024);
     }
-#endif
     return pick(CK_Q2, te, gp, 512);
 }
 
@@ -1527,11 +1443,9 @@ struct FinQueue {
         if (b.n) {
             int maxcols = 0;
             for (int i = 0; i < b.n; ++i) maxcols = std::max(maxcols, b.job[i].I * b.job[i].R);
-#if !defined(WG_OPT_FIN_BLOCK_ROWS)
             if (maxcols <= 1024)        // one wave per row, four rows per block (long rows -- WSRGlow's 3659 conditioning columns -- keep a block each)
                 WG_LAUNCH(cx, finalize_batch_wave_kernel, dim3((b.start[b.n] + 3) / 4), dim3(256), (size_t)4 * maxcols * sizeof(float), b, maxcols);
             else
-#endif
                 WG_LAUNCH(cx, finalize_batch_kernel, dim3(b.start[b.n]), dim3(256), 0, b);
         }
         b.n = 0;
@@ -1581,13 +1495,10 @@ WgradOut run_wgrad(Ctx &cx, const Geo &g, const WSegSpec *sa, int nsa, const WSe
         q.cpb = g.Tt / WG16_BK; q.total_chunks = g.B * q.cpb;
         // 256-row tiles (8 waves, one workgroup per CU): 25 % less operand stream for the same MFMAs, but MEASURED SLOWER (155 us
         // against 137 us per launch at the headline shape, parity identical): one 8-wave workgroup in barrier lockstep hides less
-        // latency than two independent 4-wave ones.  Opt-in A/B build only.
-        const bool tall = a.Mp % 256 == 0
-#if !defined(WG_OPT_WGRAD_TALL)
-                          && false
-#endif
-            ;
-        q.nsplit = plan_wgrad_flat(g, (a.Mp / WG_TILE) * (a.Np / WG_TILE));   // tall: half the tiles for half the slots -- the same split
+        // latency than two independent 4-wave ones.  Never taken; the branch below is what keeps wgrad16s_kernel<2> compiled for
+        // tools/check_asm_loads.py, which counts it.
+        const bool tall = false;
+        q.nsplit = plan_wgrad_flat(g, (a.Mp / WG_TILE) * (a.Np / WG_TILE));
         o.nsplit = q.nsplit;
         if ((size_t)q.nsplit * a.Mp * a.Np > slab_cap) { if (!cx.err) cx.err = WG_EWORKSPACE; return o; }
         grid.z = q.nsplit;
@@ -1659,9 +1570,6 @@ static bool shape_wgrad_group(Ctx &cx, const Geo &g, const WgradGroupSpec *gs, i
     q.Np = rup(blk * 32, WG_TILE);
     const int tiles = (q.Mp / WG_TILE) * (q.Np / WG_TILE);
     q.nsplit = plan_wgrad_flat(g, tiles * ng);
-#if defined(WG_OPT_GRP_NSPLIT_MUL)                             // experiment: more, shorter workgroups (and more slab bytes)
-    q.nsplit = std::min(q.nsplit * WG_OPT_GRP_NSPLIT_MUL, std::max(1, q.total_chunks / 4));
-#endif
     while (q.nsplit > 1 && rupz((size_t)q.nsplit * ng * q.Mp * q.Np, 64) > cx.fq->cap) --q.nsplit;
     q.ngroups = ng;
     if (rupz((size_t)q.nsplit * ng * q.Mp * q.Np, 64) > cx.fq->cap) { if (!cx.err) cx.err = WG_EWORKSPACE; return false; }
@@ -1711,15 +1619,10 @@ void run_wgrad_group_pair(Ctx &cx, const Geo &g, const WgradGroupSpec *gs0, int 
     if (g.rows == 0 && pp.p[0].Mp % 256 == 0 && pp.p[1].Mp % 256 == 0)
         plan = plan_wgt_any(pp.p[0].Mp / 256, pp.p[0].Np / WG_TILE, pp.p[1].Mp / 256, pp.p[1].Np / WG_TILE, ng, pp.p[0].total_chunks);
     if (plan.ok) { pp.p[0].nsplit = plan.nslab[0]; pp.p[1].nsplit = plan.nslab[1]; }
-    // progress counters of the (group, split) sets of both products (soft lock-step, wg_gemm16s.h): one 128-byte line each
-    const size_t nctr0 = (size_t)pp.p[0].nsplit * ng, nctr1 = (size_t)pp.p[1].nsplit * ng;
-    size_t sync_floats = rupz((nctr0 + nctr1) * WG_SYNC_STRIDE, 64);
-#if !defined(WG_OPT_WGRAD_SYNC)                              // measured: holds the HBM traffic at the operand bytes and costs more than that saves
-    sync_floats = 0;
-#endif
-    if (plan.ok) sync_floats = 0;
-    if (group_slab_floats(pp.p[0]) + group_slab_floats(pp.p[1]) + sync_floats > cx.fq->cap) { if (!cx.err) cx.err = WG_EWORKSPACE; return; }   // (wn_ws_layout sizes for it)
-    cx.fq->ensure(group_slab_floats(pp.p[0]) + group_slab_floats(pp.p[1]) + sync_floats);    // all live until the launch: no wrap between them
+    // (the soft lock-step of the (group, split) sets, wg_gemm16s.h, is not armed -- WgradSArgs::sync stays nullptr.  tried, measured: it
+    // holds the HBM traffic at the operand bytes and costs more than that saves; code: git show 9da18f4:constant-memory-waveglow_amd/csrc/wgflow.hip)
+    if (group_slab_floats(pp.p[0]) + group_slab_floats(pp.p[1]) > cx.fq->cap) { if (!cx.err) cx.err = WG_EWORKSPACE; return; }   // (wn_ws_layout sizes for it)
+    cx.fq->ensure(group_slab_floats(pp.p[0]) + group_slab_floats(pp.p[1]));    // all live until the launch: no wrap between them
     if (!bind_wgrad_group(cx, gs0, zero_plane, outs0, pp.p[0]) || !bind_wgrad_group(cx, gs1, zero_plane, outs1, pp.p[1])) return;
     if (plan.ok) {
         WgtArgs wa;
@@ -1755,12 +1658,6 @@ void run_wgrad_group_pair(Ctx &cx, const Geo &g, const WgradGroupSpec *gs0, int 
         WG_LAUNCH(cx, wgrad16t_kernel, dim3(256), dim3(768), 0, wa);
         g_wgrad16t_launches.fetch_add(1, std::memory_order_relaxed);
         return;
-    }
-    if (sync_floats) {
-        unsigned *ctr = reinterpret_cast<unsigned *>(cx.fq->reserve(sync_floats));
-        if (cx.err) return;
-        if (hipMemsetAsync(ctr, 0, sync_floats * sizeof(float), cx.st) != hipSuccess) { cx.err = WG_ELAUNCH; return; }
-        pp.p[0].sync = ctr; pp.p[1].sync = ctr + nctr0 * WG_SYNC_STRIDE;
     }
     for (int w = 0; w < 2; ++w) {
         pp.gx[w] = pp.p[w].Np / WG_TILE; pp.gy[w] = pp.p[w].Mp / WG_TILE;
@@ -1876,12 +1773,8 @@ static size_t thin_end_lds(const WnD &d) { const int k2p = thin_k2p(d); return (
 // products + convs)
 static bool thin_shape_ok(const WnD &d)
 {
-#if defined(WG_OPT_NO_THIN)
-    return false;
-#else
     return !d.bias && d.ic <= 16 && d.C % 8 == 0 && d.Cs % 8 == 0 && d.C <= WGTH_MAXROWS * WGTH_THREADS && d.Cs <= WGTH_MAXROWS * WGTH_THREADS &&
            thin_start_lds(d) <= WG_LDS_BYTES && thin_end_lds(d) <= WG_LDS_BYTES;
-#endif
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1894,9 +1787,6 @@ std::atomic<long long> g_layer_launches{0};                   // diagnostics: la
 template <class FA, class FB>
 bool run_convlayer(Ctx &cx, float *ws, size_t lsync, FA &&gate_call, FB &&wo_call)
 {
-#if defined(WG_OPT_NO_LAYER)
-    return false;
-#else
     if (cx.prec != 2 || cx.rec || cx.err) return false;
     {   // OPT-IN (WG_LAYER_FUSION=1 in the environment).  Measured on MI355X (gpurun_out/r04e_stress.txt): parity
         // identical, and no faster than the two launches it replaces -- 2.72 against 2.65-2.76 ms per 0.7 s utterance, 95.7 against 95.8 ms
@@ -1929,18 +1819,17 @@ bool run_convlayer(Ctx &cx, float *ws, size_t lsync, FA &&gate_call, FB &&wo_cal
     WG_LAUNCH(cx, convlayer16h_kernel<EPI_RESSKIP>, dim3(grid), dim3(512), 0, la);
     g_layer_launches.fetch_add(1, std::memory_order_relaxed);
     return true;
-#endif
 }
 // A product of a one-launch layer below as its 256 x 128-tile argument block (ntx x nty x ntz tiles of 256 rows, plane rows dealt to the
 // XCDs where they divide by 8): the gate conv or a store with an S-plane-only epilogue, on more 128 x 128 tiles than the small grids take,
 // over every plane row.  false: the product does not qualify.
 static bool layer_args(const Ctx &cx, const ConvOp &op, ConvGemm16sArgs &as)
 {
-    const bool sg = op.epi == EPI_GATE && op.s0.hi && !op.out0.p && WG_TS_INTERLEAVED;
+    const bool sg = op.epi == EPI_GATE && op.s0.hi && !op.out0.p;
     const bool se = op.epi == EPI_STORE && op.s0.hi && !op.out0.p && !op.aux0.p;
     if (cx.prec != 2 || cx.rec || cx.row_sel1 || op.g.rows != 0 || !(sg || se) || rup(op.M, WG_TILE) % 256) return false;
     const ConvRoute rt = conv_args(cx, op);
-    if (rt.err || conv_small(op, rt.grid)) return false;
+    if (rt.err || conv_small(rt.grid)) return false;
     as = rt.as;
     as.ntx = (int)rt.grid.x; as.nty = (int)rt.grid.y / 2; as.ntz = (int)rt.grid.z;
     as.xcd_items = as.ntz % 8 == 0 ? as.ntz / 8 : 0;
@@ -1952,9 +1841,6 @@ static bool layer_args(const Ctx &cx, const ConvOp &op, ConvGemm16sArgs &as)
 std::atomic<long long> g_layerq_launches{0};                  // diagnostics: launches of convlayer16q_kernel (wg_stat_layerq_launches)
 bool run_convlayer_big(Ctx &cx, float *ws, size_t lsync, const ConvOp &gate, const ConvOp &res)
 {
-#if defined(WG_OPT_NO_LAYERQ)
-    return false;
-#else
     if (cx.prec != 2 || cx.rec || cx.err) return false;
     {
         // OPT-IN (WG_LAYER_FUSION_BIG=1).  Measured at the headline shape (gpurun_out/r04g_bigfuse.txt, r04h_bisect.txt):
@@ -1989,7 +1875,6 @@ bool run_convlayer_big(Ctx &cx, float *ws, size_t lsync, const ConvOp &gate, con
     WG_LAUNCH(cx, convlayer16q_kernel, dim3(cus), dim3(1024), 0, la);
     g_layerq_launches.fetch_add(1, std::memory_order_relaxed);
     return true;
-#endif
 }
 
 // The layer as ONE launch of convlayer16g_kernel (wg_gemm16g.h): a workgroup owns whole 192-column tiles, computes both 256-row gate tiles
@@ -1998,9 +1883,6 @@ bool run_convlayer_big(Ctx &cx, float *ws, size_t lsync, const ConvOp &gate, con
 std::atomic<long long> g_layerg_launches{0};                  // diagnostics (wg_stat_layer_launches)
 bool run_convlayer_g(Ctx &cx, const ConvOp &gate, const ConvOp &res)
 {
-#if defined(WG_OPT_NO_G192) || defined(WG_OPT_NO_LAYERG)
-    return false;
-#else
     // (WG_LAYER_FUSION_BIG=1 asks for the older one-launch layer instead)
     if (!env_sw().layer_g || env_sw().layer_fusion_big) return false;
     if (!g192_on() || cx.prec != 2 || cx.rec || cx.err) return false;
@@ -2039,7 +1921,6 @@ bool run_convlayer_g(Ctx &cx, const ConvOp &gate, const ConvOp &res)
     WG_LAUNCH(cx, convlayer16g_kernel, dim3(cus), dim3(512), 0, la);
     g_layerg_launches.fetch_add(1, std::memory_order_relaxed);
     return true;
-#endif
 }
 
 // (the counters are left at zero by every launch; a call that was cut short -- an error half way -- is the reason they are cleared
@@ -2141,9 +2022,6 @@ static ConvOp wn_gate_op(const Ctx &cx, const WnRun &r, int i, int hin, bool kee
         if (fold) sg[ns++] = {r.X.p, r.X.Cp, r.X.ch0, r.L.kp_start, ts, ws + r.w.XaS, r.L.kp_start, 0, ro, 0};    // (xa's S-plane: wn_forward)
         else sg[ns++] = {Hin, d.C, 0, d.C, ts, ws + r.w.HS[hin], d.C, 0, ro, 0};
     }
-#if defined(WG_DBG_NOCOND)      // timing experiment only (results are garbage): the gate conv without its conditioning segment
-    if (false)
-#endif
     sg[ns++] = {r.Y, d.auxp(), 0, d.auxp(), 0, r.YS, d.auxp(), 0, 0, d.mode2d};
     if (nb) sg[ns++] = ones_seg(cx, r);                      // (wn_forward filled the plane of ones at the start of the pass)
     ConvOp op = conv_op(g, r.pk + (fold ? r.L.Acat0x : r.L.Acat[i]), r.L.ld_Acat, 2 * d.Cd, sg, ns, EPI_GATE, sp ? pnull() : pref(gate, d.Cd),
@@ -2195,11 +2073,7 @@ void wn_forward(Ctx &cx, const WnRun &r)
     // WN.start on the vector ALU in ONE launch (start_fwd_kernel, wg_thin.h) instead of an S-plane conversion + an MFMA conv on a K of 2-4
     // channels; a pass that keeps its activations takes it only where the backward's thin start product reads xa itself (thin_shape_ok)
     // -- the MFMA weight gradient would want xa's S-plane
-    const bool vstart = sp && !nb && !cx.rec && d.ic <= 16 && d.C % 8 == 0 && (!r.save || thin_shape_ok(d))
-#if defined(WG_OPT_NO_VSTART)
-                        && false
-#endif
-        ;
+    const bool vstart = sp && !nb && !cx.rec && d.ic <= 16 && d.C % 8 == 0 && (!r.save || thin_shape_ok(d));
     if (r.start_done) {
         // (the seam launch of the flow visited before wrote h_0: same arithmetic as start_fwd_kernel below)
         if (start_fold_on(cx, r)) run_to_splane(cx, g, r.X, d.ic, ws + r.w.XaS, r.L.kp_start);      // (layer 0 reads xa itself: wn_gate_op)
@@ -2318,11 +2192,7 @@ bool run_inv_seam(Ctx &cx, const WnRun &r, const float *Winv, float *partial, co
 
 bool thin_ok(const Ctx &cx, const WnD &d)
 {
-#if defined(WG_OPT_NO_THIN)
-    return false;
-#else
     return cx.prec == 2 && cx.fq && !cx.rec && thin_shape_ok(d);
-#endif
 }
 static int thin_grid(int tiles)
 {
@@ -2401,11 +2271,7 @@ static const float *run_lowrank_end(Ctx &cx, const WnRun &r, const float *const 
     const int ic2 = 2 * d.ic, mrows = rup(ic2, 8), nblk = g.B * (g.Tt / 64);
     // column ranges: 8 where the unit rows alone give 64 workgroups per range (the 256-channel WN: 512 workgroups), more where they do not
     // (WaveFlow's 64 channels: 16 workgroups per range -- with 8 ranges half the chip ran this pass: 199 us for the bytes the headline's takes 105 for)
-#if defined(WG_OPT_PGATE_NCR8)                           // A/B build: eight ranges whatever the channel count (before round 6's last commit)
-    const int want = 8;
-#else
     const int wgr = (d.depth * (d.Cd / 8) + 3) / 4, want = std::min(32, std::max(8, (512 + wgr - 1) / wgr));
-#endif
     const int ncr = std::max(1, std::min(want, nblk / 4)), per = (nblk + ncr - 1) / ncr;
     const size_t n = (size_t)d.depth * mrows * d.Cd;
     PGateArgs a;
@@ -2479,9 +2345,7 @@ void wn_backward(Ctx &cx, const WnRun &r, const float *const *p, float *const *g
         if (nb && db) run_finalize(cx, slabp, wo, row0, rows, 1, 1, col0, 1, 0, nullptr, nullptr, nullptr, db);
     };
     auto gb = [&](int j) -> float * { return nb ? grads[d.pb(j)] : nullptr; };      // gradient of bias j (WnD::pb), nullable
-#if !defined(WG_OPT_NO_FIN_BATCH)
     FinQueue fq(cx, slab, cap);                               // flushed when it goes out of scope: before the caller's next launch
-#endif
     // the rank-2ic form of the skip path (lowrank_on): neither S nor dS = W_end^T G exists; G itself (as an S-plane of kp_end channels)
     // is the K segment that stands for dS in every gate backward, and the skip rows' weight gradients come from P_l = G gate_l^T
     const bool lr = lowrank_on(cx, r);
@@ -2628,9 +2492,6 @@ void wn_backward(Ctx &cx, const WnRun &r, const float *const *p, float *const *g
         WgradOut wo[WG_GRP_MAX], woO[WG_GRP_MAX];
         const int C32 = rup(d.C, 32);
         bool pair = true;
-#if defined(WG_OPT_NO_WGRAD_PAIR)
-        pair = false;
-#endif
         // (one after the other, each finalisation queued behind its own launch: the second product's slabs may then reuse the arena)
         const int nsbT = d.radix + (hv ? 0 : 1) + nb;
         if (pair) run_wgrad_group_pair(cx, g, gsT, 1, nsbT, wo, gsO, lr ? 1 : 2, 1 + nb, woO, nd, ws + r.w.dSS);
@@ -3281,7 +3142,6 @@ static int model_backward(const wg_config *cf, const void *const *params, const 
         const int c = flow_channels(cf, k);
         const float *lu = pk + M.lu + (size_t)k * WG_LU_STRIDE;
         PRef Xk = pref(ws + W.X, W.Gp, base), dXk = pref(ws + W.dX, W.Gp, base);
-#if !defined(WG_OPT_NO_FUSED_INVCONV_BWD)
         const dim3 fgrid((T + 256 * WG_ICB_T - 1) / (256 * WG_ICB_T), B);
         if (c <= 8 && (c & 1) == 0 && (size_t)fgrid.x * fgrid.y * c * c <= W.wn.slab_floats) {      // one pass: x, dx and the shares of dW
             float *part = ws + W.wn.slab;
@@ -3298,7 +3158,6 @@ static int model_backward(const wg_config *cf, const void *const *params, const 
                          lu + WG_MAXC * WG_MAXC, dlogdet, B, (float)T);                       // + W^-T dlogdet T :242
             return;
         }
-#endif
         run_mix(cx, g, Xk, c, lu + WG_MAXC * WG_MAXC, 0);                                     // x = W^-1 z   :235-237
         WSegSpec sa = {dXk.p, dXk.Cp, dXk.ch0, c, 0, nullptr, 0, 0}, sb = {Xk.p, Xk.Cp, Xk.ch0, c, 0, nullptr, 0, 0};
         const int prec_keep = cx.prec;
@@ -3648,72 +3507,15 @@ int wg_wf_inverse(const wg_wf_config *cf, const void *const *params, const void 
         else WG_LAUNCH(cx, wf_flip_kernel, rgrid, dim3(256), 0, pref(Z, 1), pref(Zf, 1), g);                         // :222
         WG_LAUNCH(cx, wf_copy_row_kernel, igrid, dim3(256), 0, pref(Zf, 1), pref(Xb, 1), g, 0, 0);                   // :228
         r.pk = pk + L.wn[k]; r.X = pref(Xb, 1);
-        // One row step's launches, recorded: they are the same for every row but for the row index, so ONE persistent kernel walks
-        // rows x stages on the device with a grid barrier where the launches had kernel boundaries (wg_stage.h).
-        // MEASURED and therefore OFF by default (-DWG_OPT_ROWWALK turns it on; bit-identical results): 105.8 against 99.3 ms for a 0.7 s
+        // One row step's launches are the same for every row but for the row index, so ONE persistent kernel could walk rows x stages
+        // on the device with a grid barrier where the launches have kernel boundaries (wf_rowsteps_kernel, wg_stage.h).
+        // tried, MEASURED and therefore not launched (bit-identical results; code: git show
+        // 9da18f4:constant-memory-waveglow_amd/csrc/wgflow.hip, wg_wf_inverse): 105.8 against 99.3 ms for a 0.7 s
         // utterance, 227 against 214 ms for 10 s.  A stage is not its launch overhead: the 64 x 64-tile conv of a row step is a chain of
         // 21 chunk latencies on 8 of 256 CUs (~8 us), and a grid barrier with the release / acquire fences that make planes visible
         // across XCDs (L2 write-back + invalidate) costs about what a kernel boundary does.  What the row step needs is more workgroups
         // per stage (the K range of a tile split over several CUs), see DESIGN.md section 9.
-        bool walked = false;
-#if defined(WG_OPT_ROWWALK)
-        {
-            StageRec rec;
-            cx.rec = &rec;
-            cx.row_sel1 = 1;
-            wn_forward(cx, r);
-            wf_couple(cx, r, p[3 + wf_pf(cf) * k + 36], wf_end_bias(cf, p, k), 2, pref(Zf, 1), pref(Xb, 1), pnull(), pnull(), nullptr, ws + W.rowsum + (size_t)k * g.B, 0);
-            cx.rec = nullptr;
-            cx.row_sel1 = 0;
-#if defined(WG_DBG_ROWWALK_HOSTREPLAY)   // debugging aid: the recorded program replayed launch by launch from the host
-            if (rec.ok && !cx.err) {
-                for (int row = 0; row < H - 1; ++row)
-                    for (size_t si = 0; si < rec.st.size(); ++si) {
-                        WgStage stg = rec.st[si];
-                        if (stg.kind <= WGS_CONV_RESSKIP) {
-                            stg.u.conv.c.row_sel1 = row + 1;
-                            const dim3 gh(stg.nblocks);
-                            if (stg.kind == WGS_CONV_STORE) WG_LAUNCH(cx, convgemm16h_kernel<EPI_STORE>, gh, dim3(512), 0, stg.u.conv);
-                            else if (stg.kind == WGS_CONV_GATE) WG_LAUNCH(cx, convgemm16h_kernel<EPI_GATE>, gh, dim3(512), 0, stg.u.conv);
-                            else WG_LAUNCH(cx, convgemm16h_kernel<EPI_RESSKIP>, gh, dim3(512), 0, stg.u.conv);
-                        } else if (stg.kind == WGS_TOSPLANE) {
-                            const WgsToSplane &t = stg.u.tsp;
-                            WG_LAUNCH(cx, to_splane_kernel, dim3((t.g.T + 255) / 256, t.cgs, t.g.B), dim3(256), 0, t.src, t.nvalid, t.dst, t.g);
-                        } else {
-                            stg.u.cpl.row_sel = row;
-                            WG_LAUNCH(cx, wf_couple_kernel, dim3(stg.nblocks), dim3(256), 0, stg.u.cpl);
-                        }
-                    }
-                walked = true;
-            } else
-#endif
-            if (rec.ok && !cx.err && !rec.st.empty() && rec.st.size() <= WF_PROG_STAGES) {
-                WgStage *prog = reinterpret_cast<WgStage *>(ws + W.prog);
-                unsigned *bar = reinterpret_cast<unsigned *>(reinterpret_cast<char *>(prog) + WF_PROG_STAGES * sizeof(WgStage));
-                const int n = (int)rec.st.size();
-#if defined(WG_DBG_ROWWALK_MEMCPY)       // debugging aid: the program through a host copy (the buffer is leaked on purpose)
-                {
-                    WgStage *keep = new WgStage[n];
-                    memcpy(static_cast<void *>(keep), static_cast<const void *>(rec.st.data()), (size_t)n * sizeof(WgStage));
-                    if (hipMemcpyAsync(prog, keep, (size_t)n * sizeof(WgStage), hipMemcpyHostToDevice, cx.st) != hipSuccess) cx.err = WG_ELAUNCH;
-                }
-                for (int i = n; i < n; i += WGS_PER_STORE) {
-#else
-                for (int i = 0; i < n; i += WGS_PER_STORE) {
-#endif
-                    WgsStoreArgs sa;
-                    const int m = std::min(WGS_PER_STORE, n - i);
-                    memcpy(static_cast<void *>(sa.st), static_cast<const void *>(&rec.st[i]), (size_t)m * sizeof(WgStage));
-                    WG_LAUNCH(cx, wgs_store_kernel, dim3(1), dim3(256), 0, sa, m, prog + i);
-                }
-                if (!cx.err && hipMemsetAsync(bar, 0, 64, cx.st) != hipSuccess) cx.err = WG_ELAUNCH;
-                const int grid = std::max(1, std::min(rec.widest, device_cus()));     // every workgroup resident: the barrier needs them all
-                WG_LAUNCH(cx, wf_rowsteps_kernel, dim3(grid), dim3(WGS_THREADS), 0, (const WgStage *)prog, n, H - 1, bar, (int *)(bar + 8));
-                walked = true;
-            }
-        }
-#endif
-        for (int row = 0; row < H - 1 && !walked; ++row) {
+        for (int row = 0; row < H - 1; ++row) {
             cx.row_sel1 = row + 1;
             wn_forward(cx, r);
             wf_couple(cx, r, p[3 + wf_pf(cf) * k + 36], wf_end_bias(cf, p, k), 2, pref(Zf, 1), pref(Xb, 1), pnull(), pnull(), nullptr,
@@ -3723,13 +3525,9 @@ int wg_wf_inverse(const wg_wf_config *cf, const void *const *params, const void 
         std::swap(Z, Xb);
     }
     // rowsum rows H-1 are never written by mode 2: they were zeroed with the workspace
-    // (the row walk's failure word is only ever written by the -DWG_OPT_ROWWALK build: the default build must not read a workspace
-    // region nothing initialises -- a workspace that served another layout could turn every logdet into NaN)
-#if defined(WG_OPT_ROWWALK)
-    const int *walk_fail = reinterpret_cast<const int *>(reinterpret_cast<const char *>(ws + W.prog) + WF_PROG_STAGES * sizeof(WgStage)) + 8;
-#else
+    // (the row walk's failure word is only ever written by wf_rowsteps_kernel, which nothing launches: a workspace region nothing
+    // initialises must not be read -- a workspace that served another layout could turn every logdet into NaN)
     const int *walk_fail = nullptr;
-#endif
     WG_LAUNCH(cx, wf_logdet_kernel, dim3((B + 63) / 64), dim3(64), 0, ws + W.rowsum, cf->flows, B, H, logdet,
               cf->use_conv1x1 ? pk + L.mix : (const float *)nullptr, L.mix_stride, -(float)g.T, walk_fail);          // :227-229
     WG_LAUNCH(cx, wf_unsqueeze_kernel, rgrid, dim3(256), 0, pref(Z, 1), g, N, x);

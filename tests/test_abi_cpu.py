@@ -161,7 +161,7 @@ def test_hand_issued_loads_are_never_touched_before_their_wait():
     # heights + the paired launch; wgrad16t; the stage interpreter wf_rowsteps_kernel (three convgemm16h bodies inside); the one-launch
     # layers convlayer16h_kernel (two convgemm16h-shaped phases, the second with sc1 operand loads) and convlayer16q_kernel (the 256 x 128
     # form walking a list of gate and residual tiles); five 64-row (M64) and two column-group (CG2) instantiations of convgemm16q.  (The superseded
-    # 32x32x16 kernels left the tree: a build with -DWG_OPT_MFMA32 stops at the #error in wg_gemm16s.h.)
+    # 32x32x16 kernels left the tree: git show 4c099e9:tools/experiments/wg_gemm16_superseded.h.)
     # convgemm16g_kernel (LDS-DMA, no register-destination loads): the instruction counts behind its counted waits: four epilogues (gate, S-plane store, fp32 store, the K parts of a split product) and
     # the one-launch layer convlayer16g_kernel (two products one after the other)
     dma = [l for l in r.stdout.splitlines() if "LDS-DMA instructions" in l]

@@ -1,6 +1,7 @@
-"""Phase timeline of the gate conv (developer experiment): needs a -DWG_DBG_TRACE build of libwgflow.so.
+"""Phase timeline of the gate conv (developer experiment): needs a -DWG_DBG_TRACE build of libwgflow.so
+(build(True, defines=["WG_DBG_TRACE"], out=...) of constant-memory-waveglow_amd/build.py).
 
-    WGFLOW_LIB=.../variants/trace.so python tools/experiments/conv_trace.py
+    WGFLOW_LIB=/path/to/trace.so python tools/experiments/conv_trace.py
 
 Runs one coupling forward at the C2 shape, then prints per workgroup slot: start, first barrier, and for each of its tiles the
 end of the main loop and the end of the epilogue (us, relative to the earliest workgroup start of the LAST gate-conv launch)."""

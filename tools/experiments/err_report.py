@@ -1,6 +1,6 @@
 """Error margins of the HIP engine against the reference goldens / the oracle (developer tool; prints, asserts nothing).
 
-    [WGFLOW_LIB=variants/lib_x.so] python tools/experiments/err_report.py
+    [WGFLOW_LIB=/path/to/other.so] python tools/experiments/err_report.py
 
 For micro / c1 (oracle + golden) and c2 (golden): max |dz|, |dloss|, worst parameter-gradient error relative to the tensor's max."""
 import os

@@ -1,7 +1,7 @@
-"""Phase stamps of convlayer16g_kernel (developer experiment; -DWG_DBG_TRACE build): the gate product's and the residual product's
+"""Phase stamps of convlayer16g_kernel (developer experiment; -DWG_DBG_TRACE -DWGG_TRACE_LAYER build): the gate product's and the residual product's
 timeline inside ONE launch, microseconds from the first workgroup's entry (mean / max over the 256 workgroups).
 
-    WGFLOW_LIB=variants/lib_gltrace.so python tools/experiments/g192_layer_trace.py"""
+    WGFLOW_LIB=/path/to/trace.so python tools/experiments/g192_layer_trace.py"""
 import ctypes as C
 import os
 import sys

@@ -1,6 +1,7 @@
-"""Phase stamps of convgemm16g_kernel<EPI_GATE_SO> (developer experiment): needs a -DWG_DBG_TRACE build of libwgflow.so.
+"""Phase stamps of convgemm16g_kernel<EPI_GATE_SO> (developer experiment): needs a -DWG_DBG_TRACE build of libwgflow.so
+(build(True, defines=["WG_DBG_TRACE"], out=...) of constant-memory-waveglow_amd/build.py).
 
-    WGFLOW_LIB=variants/lib_gtrace.so python tools/experiments/g192_trace.py
+    WGFLOW_LIB=/path/to/trace.so python tools/experiments/g192_trace.py
 
 Runs coupling forwards at the C2 shape, then prints (median over the 256 workgroups of the LAST gate-conv launch, wave WGG_TRACE_WAVE):
 the cycles between the stamps inside one chunk, the tile-level timeline and the clock held."""

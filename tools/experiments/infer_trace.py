@@ -1,7 +1,7 @@
 """Phase timeline of the gate conv in single-utterance synthesis (developer experiment): needs a
--DWG_DBG_TRACE,WG_DBG_TRACE_SMALL build (stamps convgemm16h, or with WG_OPT_NO_HTILE the 128 x 64 form of convgemm16q).
+-DWG_DBG_TRACE,WG_DBG_TRACE_SMALL build (stamps convgemm16h; the 128 x 64 form of convgemm16q where a launch takes it).
 
-    WGFLOW_LIB=.../variants/lib_trsmall.so python tools/experiments/infer_trace.py [frames]
+    WGFLOW_LIB=/path/to/trace.so python tools/experiments/infer_trace.py [frames]
 """
 import ctypes as C
 import os

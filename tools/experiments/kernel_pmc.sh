@@ -1,8 +1,7 @@
-# usage: bash tools/experiments/kernel_pmc.sh <tag> [variant]: PMC passes over tools/kbench.py (one coupling forward + backward at the C2 shape) ->
-# gpurun_out/pmc_<tag>_{fetch,write,mfma,lds}/...counter_collection.csv ; with a variant name the library variants/lib_<variant>.so is used
+# usage: bash tools/experiments/kernel_pmc.sh <tag>: PMC passes over tools/kbench.py (one coupling forward + backward at the C2 shape) ->
+# <output directory>/pmc_<tag>_{fetch,write,mfma,lds}/...counter_collection.csv
 tag=${1:-x}
 R=$GRAFT_REPO_ROOT
-if [ -n "$2" ]; then export WGFLOW_LIB=$R/variants/lib_$2.so; fi
 cd /tmp && export TMPDIR=/tmp
 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $R/gpurun_out/pmc_${tag}_fetch -- python3 $R/tools/kbench.py --iters 1 > /dev/null 2>&1
 rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $R/gpurun_out/pmc_${tag}_write -- python3 $R/tools/kbench.py --iters 1 > /dev/null 2>&1

@@ -1,6 +1,7 @@
-"""Phase timeline and in-kernel clock of wgrad16t_kernel (developer experiment): needs a -DWG_DBG_TRACE build of libwgflow.so.
+"""Phase timeline and in-kernel clock of wgrad16t_kernel (developer experiment): needs a -DWG_DBG_TRACE build of libwgflow.so
+(build(True, defines=["WG_DBG_TRACE"], out=...) of constant-memory-waveglow_amd/build.py).
 
-    WGFLOW_LIB=.../variants/lib_trace.so python tools/experiments/wgrad_trace.py [out.json]
+    WGFLOW_LIB=/path/to/trace.so python tools/experiments/wgrad_trace.py [out.json]
 
 Runs coupling forward + backward at the C2 shape and reads the stamps of the LAST weight-gradient launch: per workgroup (= CU) start,
 first barrier, end of the main loop and of the slab store of each of its items; shader cycles / wall time = the clock held; the spread of
