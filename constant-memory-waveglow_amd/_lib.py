@@ -27,6 +27,7 @@ ABI_SYMBOLS = [
     "wg_reload_env", "wg_stat_gate_part_launches", "wg_wsr_cond_pre",
     "wg_mg_gemm_workspace_bytes", "wg_mg_gemm", "wg_mg_bn_stats", "wg_mg_bn_update", "wg_mg_bn_tanh", "wg_mg_bn_tanh_backward", "wg_mg_weight_norm",
     "wg_mg_weight_norm_backward", "wg_lvc_check", "wg_lvc_forward", "wg_lvc_backward_data", "wg_lvc_backward_weight", "wg_lvc_gate_backward",
+    "wg_mr_haar_split", "wg_mr_haar_merge", "wg_mr_upsample", "wg_mr_upsample_backward", "wg_mr_pack", "wg_mr_unpack",
 ]
 K_CONV_STORE, K_CONV_GATE, K_CONV_RESSKIP, K_CONV_DGATE, K_WGRAD, K_LAYER, K_THIN = range(7)
 
@@ -195,6 +196,13 @@ def lib():
     L.wg_lvc_backward_data.argtypes = [lvcp, vp, vp, vp, i, i, i, vp, vp]
     L.wg_lvc_backward_weight.argtypes = [lvcp, vp, vp, i, i, i, vp, vp]
     L.wg_lvc_gate_backward.argtypes = [vp, vp, i, i, i, vp, vp]
+    i64 = C.c_int64
+    L.wg_mr_haar_split.argtypes = [vp, i64, i64, i64, i, i, i, i, vp, vp, vp, i, vp]
+    L.wg_mr_haar_merge.argtypes = [vp, vp, i, vp, i, i, i, i, vp, i64, i64, i64, vp]
+    L.wg_mr_upsample.argtypes = [vp, vp, i, i, i, i, i, vp, i, i, vp]
+    L.wg_mr_upsample_backward.argtypes = [vp, i, i, i, i, i, i, i, vp, vp]
+    L.wg_mr_pack.argtypes = [vp, i, i, i, i, i, vp, vp]
+    L.wg_mr_unpack.argtypes = [vp, i, i, i, i, i, vp, vp]
     _LIB = L
     return L
 

@@ -18,6 +18,7 @@
 #include "wg_thin.h"
 #include "wg_probe.h"
 #include "wg_lvc.h"
+#include "wg_mr.h"
 
 #include <algorithm>
 #include <atomic>

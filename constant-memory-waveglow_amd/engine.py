@@ -910,3 +910,60 @@ def lvc_gate_backward(z, dgate):
     dz = torch.empty_like(z)
     check(_lib.lib().wg_lvc_gate_backward(_p(z), _p(dgate), Bn, D, T, _p(dz), _stream(z.device)), "wg_lvc_gate_backward")
     return dz
+
+
+# ---- MRWaveGlow's plumbing (csrc/wg_mr.h): one launch each, the caller's tensors in and out -------------------------------------------
+def _f32(shape, like):
+    return torch.empty(shape, dtype=torch.float32, device=like.device)
+
+
+def mr_haar_split(x, mode=0, cond_rows=0):
+    """x [B, c, T] with any strides -> (diff, avg, cond): cond [B, cond_rows, T] (None when cond_rows is 0) has avg in its first rows."""
+    Bn, c, T = x.shape
+    diff, avg = _f32((Bn, c // 2, T), x), _f32((Bn, c // 2, T), x)
+    cond = _f32((Bn, cond_rows, T), x) if cond_rows else None
+    check(_lib.lib().wg_mr_haar_split(_p(x), x.stride(0), x.stride(1), x.stride(2), Bn, c, T, mode, _p(diff), _p(avg), _p(cond), cond_rows,
+                                      _stream(x.device)), "wg_mr_haar_split")
+    return diff, avg, cond
+
+
+def mr_haar_merge(avg, diff, mode=0, channels_last=False, avg2=None):
+    """(avg, diff) [B, c/2, T] -> [B, c, T], contiguous or (channels_last) as a view of a [B, T, c] tensor; avg2: rows of a
+    [B, rows, T] tensor added to avg first."""
+    Bn, half, T = avg.shape
+    out = _f32((Bn, T, 2 * half), avg).transpose(1, 2) if channels_last else _f32((Bn, 2 * half, T), avg)
+    check(_lib.lib().wg_mr_haar_merge(_p(avg), _p(avg2), 0 if avg2 is None else avg2.size(1), _p(diff), Bn, 2 * half, T, mode, _p(out),
+                                      out.stride(0), out.stride(1), out.stride(2), _stream(avg.device)), "wg_mr_haar_merge")
+    return out
+
+
+def mr_upsample(h, s, T, out=None, r0=0, head=None):
+    """h [B, n_mels, F] -> rows [r0, r0 + n_mels) of out [B, rows, T] (a new [B, r0 + n_mels, T] by default); head [B, r0, T] fills the
+    rows before them."""
+    Bn, n_mels, F = h.shape
+    if out is None:
+        out = _f32((Bn, r0 + n_mels, T), h)
+    check(_lib.lib().wg_mr_upsample(_p(h), _p(head), Bn, n_mels, F, s, T, _p(out), out.size(1), r0, _stream(h.device)), "wg_mr_upsample")
+    return out
+
+
+def mr_upsample_backward(dout, r0, n_mels, F, s):
+    Bn, rows, T = dout.shape
+    dh = _f32((Bn, n_mels, F), dout)
+    check(_lib.lib().wg_mr_upsample_backward(_p(dout), rows, r0, Bn, n_mels, F, s, T, _p(dh), _stream(dout.device)), "wg_mr_upsample_backward")
+    return dh
+
+
+def mr_pack(src, n_group, off, dst):
+    """src [B, c, T] into channels [off, off + c) of the latent dst [B, T * n_group]"""
+    Bn, c, T = src.shape
+    check(_lib.lib().wg_mr_pack(_p(src), Bn, c, T, n_group, off, _p(dst), _stream(src.device)), "wg_mr_pack")
+    return dst
+
+
+def mr_unpack(src, n_group, off, c):
+    """channels [off, off + c) of the latent src [B, T * n_group] -> [B, c, T]"""
+    Bn, T = src.size(0), src.size(1) // n_group
+    dst = _f32((Bn, c, T), src)
+    check(_lib.lib().wg_mr_unpack(_p(src), Bn, c, T, n_group, off, _p(dst), _stream(src.device)), "wg_mr_unpack")
+    return dst

@@ -430,6 +430,34 @@ int wg_lvc_backward_data(const wg_lvc_dims *d, const float *dz, const float *w, 
 int wg_lvc_backward_weight(const wg_lvc_dims *d, const float *dz, const float *x, int B, int T, int F, float *dw, void *stream);
 int wg_lvc_gate_backward(const float *z, const float *dgate, int B, int D, int T, float *dz, void *stream);
 
+/* ---- MRWaveGlow (model/mr_waveglow.py upstream): the multi-resolution plumbing around its couplings --------------------------
+ * Appended to revision 10 without changing any earlier declaration (purely additive: the revision stays 10).  The couplings
+ * themselves are wg_coupling_* / wg_invconv_*; these six launches are what is left: exact fp32, no workspace, no atomics, the same
+ * bits in every WG_PREC_* mode and on every run.  Every one checks its arguments first and launches nothing when it returns an error.
+ *
+ * haar_split: x[b][ch][t] at x + s_b*b + s_c*ch + s_t*t (element strides >= 0, so level 0 reads the audio's [B, T, n_group] layout
+ *   as it is), c even: diff[b][i][t] = a (x[2i+1] - x[2i]), avg[b][i][t] = b (x[2i] + x[2i+1]), both [B][c/2][T] contiguous, and
+ *   (cond nullable) the same avg into rows [0, c/2) of cond[B][cond_rows][T].  mode 0: (a, b) = (1, 1/2), a level of the forward pass
+ *   (mr_waveglow.py:73-74); mode 1: (1/2, 1), the backward of haar_merge (davg = dz0 + dz1, ddiff = (dz1 - dz0) / 2).
+ * haar_merge: out[b][2i][t] = a m - b diff, out[b][2i+1][t] = a m + b diff with m = avg (+ avg2[b][i][t] of [B][avg2_rows][T],
+ *   nullable), out by element strides (o_c, o_t >= 1).  mode 0: (1, 1/2), the merge of the reverse pass (:126-127); mode 1: (1/2, 1), the backward of
+ *   haar_split (dx0 = davg / 2 - ddiff, dx1 = davg / 2 + ddiff; avg2 = the rows of the conditioning buffer's gradient).
+ * upsample: F.interpolate(h[B][n_mels][F], scale_factor = s, mode = 'linear') (:133-134, align_corners false) cut to its first T
+ *   columns (T <= F s, else WG_ESHAPE), into rows [r0, r0 + n_mels) of out[B][rows][T]; head (nullable, [B][r0][T]) is copied to rows
+ *   [0, r0) by the same launch, which makes out = cat([head, y], 1).  Column t reads position (2t + 1 - s) / (2s): below 0 it is frame
+ *   0, else frames i0 = p / 2s and min(i0 + 1, F - 1) with weights from the integer remainder (a clamped pair is the frame itself).
+ * upsample_backward: dh[B][n_mels][F] from rows [r0, r0 + n_mels) of dout[B][rows][T]: every frame sums, in column order, the at
+ *   most 2s columns that read it (0 for a frame past the cut).
+ * pack / unpack: src[B][c][T] -> dst[b][t][off + ch] of the latent [B][T][n_group] (mr_waveglow.py:93), and back (:98-106). */
+int wg_mr_haar_split(const float *x, int64_t s_b, int64_t s_c, int64_t s_t, int B, int c, int T, int mode, float *diff, float *avg,
+                     float *cond, int cond_rows, void *stream);
+int wg_mr_haar_merge(const float *avg, const float *avg2, int avg2_rows, const float *diff, int B, int c, int T, int mode, float *out,
+                     int64_t o_b, int64_t o_c, int64_t o_t, void *stream);
+int wg_mr_upsample(const float *h, const float *head, int B, int n_mels, int F, int s, int T, float *out, int rows, int r0, void *stream);
+int wg_mr_upsample_backward(const float *dout, int rows, int r0, int B, int n_mels, int F, int s, int T, float *dh, void *stream);
+int wg_mr_pack(const float *src, int B, int c, int T, int n_group, int off, float *dst, void *stream);
+int wg_mr_unpack(const float *src, int B, int c, int T, int n_group, int off, float *dst, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
