@@ -2707,6 +2707,8 @@ void wf_couple(Ctx &cx, const WnRun &r, const float *endw, const float *endb, in
     a.G = pref(r.ws + r.w.G, r.L.kp_end);
     a.dld = dld; a.rowsum = rowsum; a.row_sel = row_sel; a.g = r.g; a.mode = mode; a.noflip = noflip;
     if (cx.rec && mode == 2) { cx.rec->add(WGS_WFCOUPLE, r.g.B / r.g.rows).u.cpl = a; return; }
+    // (wn_check demands Cs % 32 == 0 of every WN, so Cs % 4 == 0 holds for every launch that gets here: no call reaches the inverse through
+    // wf_couple_kernel below, which stays for modes 0 and 1.  The quarters of wf_couple_row_kernel need the condition; it is kept as a guard.)
     if (mode == 2 && a.Cs % 4 == 0) { WG_LAUNCH(cx, wf_couple_row_kernel, dim3(r.g.B / r.g.rows), dim3(1024), 0, a); return; }
     WG_LAUNCH(cx, wf_couple_kernel, dim3(mode == 2 ? r.g.B / r.g.rows : r.g.B), dim3(256), 0, a);
 }

@@ -72,14 +72,14 @@ static int h_dilations(int n_group, int *hd)
 
 /* ---- invertible 1x1 over the height axis (efficient_modules.py:17-54) ------------------------------------------------------ */
 /* LU with partial pivoting: log|det|, sign and (optionally) the inverse of a c x c matrix */
-static void lu_logdet_inverse(const real *W, int c, real *logabs, int *sign, real *Winv)
+static void lu_logdet_inverse(const real *W, int c, double *logabs, int *sign, real *Winv)
 {
     real *a = ralloc((size_t)c * c), *yv = ralloc(c);
     int *perm = (int *)xmalloc(sizeof(int) * c);
     memcpy(a, W, sizeof(real) * c * c);
     for (int i = 0; i < c; ++i) perm[i] = i;
     int sg = 1;
-    real la = 0;
+    double la = 0;                                     /* (in double in both builds, like every logdet sum below) */
     for (int k = 0; k < c; ++k) {
         int p = k;
         real best = (real)fabs((double)a[k * c + k]);
@@ -94,7 +94,7 @@ static void lu_logdet_inverse(const real *W, int c, real *logabs, int *sign, rea
         }
         const real piv = a[k * c + k];
         if (piv < 0) sg = -sg;
-        la += (real)log(fabs((double)piv));
+        la += log(fabs((double)piv));
         for (int r = k + 1; r < c; ++r) {
             const real f = a[r * c + k] / piv;
             a[r * c + k] = f;
@@ -118,14 +118,14 @@ static void lu_logdet_inverse(const real *W, int c, real *logabs, int *sign, rea
         }
     free(a); free(yv); free(perm);
 }
-typedef struct { real *W, *Wi, ld; } mix_w;           /* ld = logdet W (NaN if det < 0, as torch.logdet) */
+typedef struct { real *W, *Wi; double ld; } mix_w;    /* ld = logdet W (NaN if det < 0, as torch.logdet) */
 static void mix_w_build(const float *w, int H, mix_w *m)
 {
     m->W = ralloc((size_t)H * H); m->Wi = ralloc((size_t)H * H);
     for (int i = 0; i < H * H; ++i) m->W[i] = (real)w[i];
-    real la; int sg;
+    double la; int sg;
     lu_logdet_inverse(m->W, H, &la, &sg, m->Wi);
-    m->ld = sg > 0 ? la : (real)NAN;
+    m->ld = sg > 0 ? la : (double)NAN;
 }
 /* out[o][t] = sum_h M[o][h] x[h][t]   (transpose: M[h][o]) */
 static void hmix(const real *M, int H, int Wd, const real *x, real *out, int transpose)
@@ -372,7 +372,10 @@ WFO_API int wfo_forward(const wfo_config *cf, const float *const *params, const 
         real *ls = ralloc((size_t)R * Wd), *tt = ralloc((size_t)R * Wd);
         upsample_fwd(cf, wup, params[0], mel + (long)b * cf->n_mels * F, F, Wd, y, NULL);
         squeeze_in(audio + (long)b * N, H, Wd, x);
-        real ld = 0;
+        /* The logdet is accumulated in double in the float build too: it is a sum of (H - 1) W log_s terms per flow that largely cancel, the
+           reference's torch.sum adds them pairwise, and one float accumulator walking 1 600+ terms in order sat 1.8e-4 from the reference
+           at 128 rows (tests/golden/wf/model_wf128c.npz) where float64 agrees to 1e-6.  The terms themselves stay in `real`. */
+        double ld = 0;
         for (int k = 0; k < cf->flows; ++k) {
             wn_forward(cf, &fw[k], hd, x, y, R, Wd, ls, tt, NULL);
             /* xout[r] = x[r+1] exp(ls[r]) + t[r] ; x_next = cat(flip(xout), x0), or W cat(x0, xout) with the 1x1   waveflow.py:198-206 */
@@ -380,12 +383,12 @@ WFO_API int wfo_forward(const wfo_config *cf, const float *const *params, const 
                 for (int t = 0; t < Wd; ++t) {
                     const long e = (long)r * Wd + t;
                     xn[(long)(conv ? r + 1 : R - 1 - r) * Wd + t] = x[(long)(r + 1) * Wd + t] * (real)exp((double)ls[e]) + tt[e];
-                    ld += ls[e];
+                    ld += (double)ls[e];
                 }
             memcpy(xn + (long)(conv ? 0 : H - 1) * Wd, x, sizeof(real) * Wd);
             if (conv) {
                 hmix(mw[k].W, H, Wd, xn, x, 0);                      /* efficient_modules.py:40 */
-                ld += (real)Wd * mw[k].ld;                           /* :39, waveflow.py:206 */
+                ld += (double)Wd * mw[k].ld;                         /* :39, waveflow.py:206 */
             } else {
                 real *tmp = x; x = xn; xn = tmp;
             }
@@ -422,13 +425,13 @@ WFO_API int wfo_inverse(const wfo_config *cf, const float *const *params, const 
         wn_saved_alloc(cf, R, Wd, &sv);
         upsample_fwd(cf, wup, params[0], mel + (long)b * cf->n_mels * F, F, Wd, y, NULL);
         squeeze_in(z + (long)b * N, H, Wd, zc);
-        real ld = 0;
+        double ld = 0;                                              /* (double in both builds: see wfo_forward) */
         for (int k = cf->flows - 1; k >= 0; --k) {
             const flow_w *w = &fw[k];
             if (conv) {                                             /* z = W^-1 z ; logdet -= W_time logdet W   (waveflow.py:224-229) */
                 hmix(mw[k].Wi, H, Wd, zc, x, 0);
                 memcpy(zc, x, sizeof(real) * H * Wd);
-                ld -= (real)Wd * mw[k].ld;
+                ld -= (double)Wd * mw[k].ld;
             } else
             /* z = z.flip(2)  (waveflow.py:222) : rows [xout_flipped.., x0] -> [x0, xout..] */
             for (int h = 0; h < H / 2; ++h)
@@ -453,7 +456,7 @@ WFO_API int wfo_inverse(const wfo_config *cf, const float *const *params, const 
                         a += w->end[c] * sv_; bb += w->end[Cs + c] * sv_;
                     }
                     x[(long)(r + 1) * Wd + t] = (zc[(long)(r + 1) * Wd + t] - bb) / (real)exp((double)a);
-                    ld -= a;
+                    ld -= (double)a;
                 }
             }
             memcpy(zc, x, sizeof(real) * H * Wd);
@@ -645,7 +648,7 @@ WFO_API int wfo_train_step(const wfo_config *cf, const float *const *params, con
         const float *melb = mel + (long)b * M * F;
         upsample_fwd(cf, wup, params[0], melb, F, Wd, y, pre);
         squeeze_in(audio + (long)b * N, H, Wd, xs[0]);
-        real ld = 0;
+        double ld = 0;                                              /* (double in both builds: see wfo_forward) */
         real **pm = (real **)xmalloc(sizeof(real *) * nf);          /* use_conv1x1: cat(x0, xout), the input of flow k's 1x1 */
         for (int k = 0; k < nf; ++k) {
             lss[k] = ralloc((size_t)RW);
@@ -656,16 +659,16 @@ WFO_API int wfo_train_step(const wfo_config *cf, const float *const *params, con
                 for (int t = 0; t < Wd; ++t) {
                     const long e = (long)r * Wd + t;
                     dst[(long)(conv ? r + 1 : R - 1 - r) * Wd + t] = xs[k][(long)(r + 1) * Wd + t] * (real)exp((double)lss[k][e]) + tt[e];
-                    ld += lss[k][e];
+                    ld += (double)lss[k][e];
                 }
             memcpy(dst + (long)(conv ? 0 : H - 1) * Wd, xs[k], sizeof(real) * Wd);
-            if (conv) { hmix(mw[k].W, H, Wd, pm[k], xs[k + 1], 0); ld += (real)Wd * mw[k].ld; }
+            if (conv) { hmix(mw[k].W, H, Wd, pm[k], xs[k + 1], 0); ld += (double)Wd * mw[k].ld; }
         }
         squeeze_out(xs[nf], H, Wd, z + (long)b * N);
         logdet[b] = (float)ld;
         double zz = 0;
         for (long e = 0; e < HW; ++e) zz += (double)xs[nf][e] * (double)xs[nf][e];
-        loss_acc += 0.5 * zz * (double)inv_s2 - (double)ld;
+        loss_acc += 0.5 * zz * (double)inv_s2 - ld;
         /* backward */
         real *dxn = ralloc((size_t)HW), *dx = ralloc((size_t)HW), *dy = rzalloc((size_t)M * Wd);
         real *dls = ralloc((size_t)RW), *dtt = ralloc((size_t)RW);

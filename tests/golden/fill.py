@@ -248,6 +248,31 @@ WF_CONFIGS["wf64b"] = dict(WF_CONFIGS["wf64"], bias=True)
 WF_SHAPES = {"wf8": (2, 8 * 96, 3), "wf64": (2, 64 * 24, 6)}       # (batch, samples, mel frames)
 WF_SHAPES["wf8c"], WF_SHAPES["wf64c"] = WF_SHAPES["wf8"], WF_SHAPES["wf64"]
 WF_SHAPES["wf8b"], WF_SHAPES["wf64b"] = WF_SHAPES["wf8"], WF_SHAPES["wf64"]
+# The other heights of dilation_dict (waveflow.py:81-87) and column counts past one 256-column block (tests/test_gpu_waveflow_shapes.py;
+# fixtures under tests/golden/wf/, make_golden_waveflow.py).  T = samples / n_group columns; s = 256 / n_group is the upsampling stride and
+# the upsampler gives at most F s - 2 (s // 2) + 2 s + 1 of them.
+_WF32 = dict(n_mels=10, dilation_channels=32, residual_channels=32)
+WF_CONFIGS.update({
+    "wf16": dict(flows=2, n_group=16, skip_channels=32, **_WF32),      # stride 16, 33 taps; height dilations all 1
+    "wf32": dict(flows=2, n_group=32, skip_channels=64, **_WF32),      # height dilations 1,2,4,1,2,4,1,2; stride 8, 17 taps
+    "wf128": dict(flows=2, n_group=128, skip_channels=32, **_WF32),    # height dilations 1 .. 64, 1; stride 2, 5 taps
+    "wf8_long": dict(flows=2, n_group=8, n_mels=12, dilation_channels=32, residual_channels=32, skip_channels=32),
+    "wf64_long": dict(flows=2, n_group=64, skip_channels=64, **_WF32),
+    "wf8_wide": dict(flows=1, n_group=8, n_mels=12, dilation_channels=32, residual_channels=32, skip_channels=32),
+})
+WF_SHAPES.update({
+    "wf16": (2, 16 * 40, 3),
+    "wf32": (2, 32 * 33, 3),           # T = 33 = 3 * 8 - 8 + 17: the last column the upsampler produces
+    "wf128": (1, 128 * 13, 5),         # T = 13 = 5 * 2 - 2 + 5, likewise
+    "wf8_long": (3, 8 * 321, 9),       # T = 321 = 9 * 32 - 32 + 65: two blocks of 256 columns, six tiles of 64
+    "wf64_long": (1, 64 * 259, 65),    # T = 259 = 256 + 3 = 4 * 64 + 3
+    "wf8_wide": (65, 8 * 8, 1),        # 65 items, one frame
+})
+for _n in ("wf16", "wf32", "wf128", "wf8_long", "wf64_long"):
+    WF_CONFIGS[_n + "c"], WF_SHAPES[_n + "c"] = dict(WF_CONFIGS[_n], use_conv1x1=True), WF_SHAPES[_n]
+WF_CONFIGS["wf128b"], WF_SHAPES["wf128b"] = dict(WF_CONFIGS["wf128"], bias=True), WF_SHAPES["wf128"]
+# the cases with a fixture of the reference's own run (wf8_wide has none: the float64 oracle alone checks it)
+WF_SHAPE_FIXTURES = ["wf16", "wf16c", "wf32", "wf32c", "wf128", "wf128c", "wf128b", "wf8_long", "wf8_longc", "wf64_long", "wf64_longc"]
 
 
 def waveflow_inputs(tag, B, N, F, n_mels):

@@ -44,3 +44,33 @@ def test_make_golden_main_regenerates_every_fixture(tmp_path):
             elif x.size:
                 scale = max(float(np.abs(x).max()), 1e-9)
                 assert float(np.abs(x.astype(np.float64) - y.astype(np.float64)).max()) <= 1e-6 * scale + 1e-9, (f, k)
+
+
+@pytest.mark.reference
+@pytest.mark.timeout(900)
+def test_make_golden_waveflow_regenerates_the_shape_fixtures(tmp_path):
+    """tests/golden/wf/ (the WaveFlow heights and column counts of tests/test_gpu_waveflow_shapes.py) from its own recipe,
+    `python tests/golden/make_golden_waveflow.py`: the eleven cases of fill.WF_SHAPE_FIXTURES and nothing else, each within the limit for
+    a committed file, every array within the rule the WaveFlow fixtures above are held to."""
+    sys.path.insert(0, GOLD)
+    import fill
+    env = dict(os.environ, WG_GOLDEN_OUT=str(tmp_path))
+    r = subprocess.run([sys.executable, os.path.join(GOLD, "make_golden_waveflow.py")], env=env, cwd=str(tmp_path), capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-3000:]
+    committed = sorted(glob.glob(os.path.join(GOLD, "wf", "*.npz")))
+    assert len(fill.WF_SHAPE_FIXTURES) == 11
+    assert [os.path.basename(f) for f in committed] == sorted("model_%s.npz" % n for n in fill.WF_SHAPE_FIXTURES)
+    assert max(os.path.getsize(f) for f in committed) <= 1 << 20
+    for f in committed:
+        g = os.path.join(str(tmp_path), os.path.basename(f))
+        assert os.path.exists(g), "the recipe did not write %s" % os.path.basename(f)
+        a, b = np.load(f), np.load(g)
+        assert sorted(a.files) == sorted(b.files), f
+        for k in a.files:
+            x, y = a[k], b[k]
+            assert x.shape == y.shape and x.dtype == y.dtype, (f, k)
+            if x.dtype.kind not in "fc":
+                assert np.array_equal(x, y), (f, k)
+            elif x.size:                                   # (Conv2d's backward sums in thread order: ~1e-8 of a tensor's max)
+                scale = max(float(np.abs(x).max()), 1e-9)
+                assert float(np.abs(x.astype(np.float64) - y.astype(np.float64)).max()) <= 1e-6 * scale + 1e-9, (f, k)

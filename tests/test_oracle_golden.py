@@ -256,20 +256,33 @@ def test_waveflow_reverse_mode_matches_reference(golden_dir, name):
         assert abs(gn - float(G["grad_norm"][i])) <= 2e-5 * float(G["grad_norm"][i]) + 1e-12, n
 
 
-@pytest.mark.parametrize("name", ["wf8", "wf64", "wf8c", "wf64c", "wf8b", "wf64b"])
+def _wf_fixture(golden_dir, name):
+    """model_<name>.npz of a WaveFlow case: the shape cases of make_golden_waveflow.py live under wf/"""
+    return np.load(os.path.join(golden_dir, "wf" if name in fill.WF_SHAPE_FIXTURES else "", "model_%s.npz" % name))
+
+
+# (the C oracle takes about 30 s for the 64 x 259 planes of wf64_long: those two fixtures are pinned by the torch oracle below and, on the
+# GPU, held against the fixture itself)
+WF_SHAPE_C = [n for n in fill.WF_SHAPE_FIXTURES if not n.startswith("wf64_long")]
+WF_SHAPE_FLIP = [n for n in fill.WF_SHAPE_FIXTURES if not n.endswith(("c", "b"))]
+
+
+@pytest.mark.parametrize("name", ["wf8", "wf64", "wf8c", "wf64c", "wf8b", "wf64b"] + WF_SHAPE_C)
 @pytest.mark.parametrize("double", [False, True])
 def test_waveflow_matches_reference(golden_dir, name, double):
     """oracle/wf_oracle.c against the reference's WaveFlow (model/waveflow.py) run by make_golden.waveflow_fixture:
     z, logdet, loss, every parameter-gradient norm and head, d loss / d mel, and the row-by-row inverse.
     "wf8c" / "wf64c": use_conv1x1=True (an invertible 1x1 conv over the height axis instead of the flip, waveflow.py:203-206);
-    "wf8b" / "wf64b": WN2D(bias=True) (waveflow.py:77), every bias gradient stored in full."""
+    "wf8b" / "wf64b": WN2D(bias=True) (waveflow.py:77), every bias gradient stored in full.
+    "wf16*", "wf32*", "wf128*", "wf8_long*" (tests/golden/wf/, make_golden_waveflow.py): the other heights of dilation_dict -- the oracle's
+    height-dilation tables for 32 and 128 rows, the upsampler at strides 16, 8 and 2 -- and 321 columns, at the same bars."""
     from oracle import wf_oracle as wfo
     cfg = fill.WF_CONFIGS[name]
     B, N, F = fill.WF_SHAPES[name]
     specs = fill.waveflow_param_specs(cfg)
     P = fill.fill_params(specs, name + "/")
     audio, mel = fill.waveflow_inputs(name, B, N, F, cfg["n_mels"])
-    G = np.load(os.path.join(golden_dir, "model_%s.npz" % name))
+    G = _wf_fixture(golden_dir, name)
     oc = wfo.make_config(**cfg)
     assert wfo.param_count(oc) == len(specs)
     r = wfo.train_step(oc, fill.table(specs, P), audio, mel, fill.SIGMA, need_dmel=True, double=double)
@@ -297,7 +310,7 @@ def test_waveflow_matches_reference(golden_dir, name, double):
     assert _logdet_close(ld, G["logdet_inv"], N)
 
 
-@pytest.mark.parametrize("name", ["wf8", "wf64", "wf8b"])
+@pytest.mark.parametrize("name", ["wf8", "wf64", "wf8b"] + WF_SHAPE_FLIP)
 @pytest.mark.parametrize("double", [False, True])
 def test_waveflow_torch_cpu_matches_reference(golden_dir, name, double):
     """oracle/torch_cpu.waveflow_train_step -- the float64-capable checker of the WaveFlow workload at its full size
@@ -310,7 +323,7 @@ def test_waveflow_torch_cpu_matches_reference(golden_dir, name, double):
     specs = fill.waveflow_param_specs(cfg)
     P = fill.fill_params(specs, name + "/")
     audio, mel = fill.waveflow_inputs(name, B, N, F, cfg["n_mels"])
-    G = np.load(os.path.join(golden_dir, "model_%s.npz" % name))
+    G = _wf_fixture(golden_dir, name)
     tab = fill.table(specs, P)
     r = tc.waveflow_train_step(cfg, tab, audio, mel, fill.SIGMA, need_dh=True, double=double)
 
