@@ -28,6 +28,8 @@ ABI_SYMBOLS = [
     "wg_mg_gemm_workspace_bytes", "wg_mg_gemm", "wg_mg_bn_stats", "wg_mg_bn_update", "wg_mg_bn_tanh", "wg_mg_bn_tanh_backward", "wg_mg_weight_norm",
     "wg_mg_weight_norm_backward", "wg_lvc_check", "wg_lvc_forward", "wg_lvc_backward_data", "wg_lvc_backward_weight", "wg_lvc_gate_backward",
     "wg_mr_haar_split", "wg_mr_haar_merge", "wg_mr_upsample", "wg_mr_upsample_backward", "wg_mr_pack", "wg_mr_unpack",
+    "wg_mg_check", "wg_mg_param_count", "wg_mg_packed_bytes", "wg_mg_workspace_bytes", "wg_mg_pack_weights", "wg_mg_forward", "wg_mg_inverse",
+    "wg_stat_mg_pass_calls", "wg_stat_mg_layer_launches", "wg_mg_layer_apply", "wg_mg_predictor_apply",
 ]
 K_CONV_STORE, K_CONV_GATE, K_CONV_RESSKIP, K_CONV_DGATE, K_WGRAD, K_LAYER, K_THIN = range(7)
 
@@ -59,6 +61,11 @@ class WgMgGemmDesc(C.Structure):
 
 class WgLvcDims(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("res_ch", "dil_ch", "radix", "dilation")]
+
+
+class WgMgConfig(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("flows", "n_group", "n_early_every", "n_early_size", "hop", "n_mels", "depth", "res_ch", "dil_ch",
+                                         "skip_ch", "radix", "pred_ch", "pred_layers", "reverse_mode")]
 
 
 PREC_F32, PREC_BF16X3, PREC_BF16X3_PLANES = 0, 1, 2
@@ -203,6 +210,22 @@ def lib():
     L.wg_mr_upsample_backward.argtypes = [vp, i, i, i, i, i, i, i, vp, vp]
     L.wg_mr_pack.argtypes = [vp, i, i, i, i, i, vp, vp]
     L.wg_mr_unpack.argtypes = [vp, i, i, i, i, i, vp, vp]
+    mgp = C.POINTER(WgMgConfig)
+    L.wg_mg_check.argtypes = [mgp, i, i, i]
+    L.wg_mg_param_count.argtypes = [mgp]
+    L.wg_mg_packed_bytes.restype = sz
+    L.wg_mg_packed_bytes.argtypes = [mgp]
+    L.wg_mg_workspace_bytes.restype = sz
+    L.wg_mg_workspace_bytes.argtypes = [mgp, i, i]
+    L.wg_mg_pack_weights.argtypes = [mgp, vp, vp, vp, vp]
+    L.wg_mg_forward.argtypes = [mgp, vp, vp, vp, i, i, i, vp, vp, vp, sz, vp]
+    L.wg_mg_inverse.argtypes = [mgp, vp, vp, vp, i, i, i, vp, vp, vp, sz, vp]
+    L.wg_stat_mg_pass_calls.restype = C.c_longlong
+    L.wg_stat_mg_pass_calls.argtypes = []
+    L.wg_stat_mg_layer_launches.restype = C.c_longlong
+    L.wg_stat_mg_layer_launches.argtypes = []
+    L.wg_mg_layer_apply.argtypes = [lvcp, i, i, i, vp, vp, vp, i, i, i, vp, vp, vp]
+    L.wg_mg_predictor_apply.argtypes = [mgp, vp, i, vp, i, i, i, vp, vp, sz, vp]
     _LIB = L
     return L
 

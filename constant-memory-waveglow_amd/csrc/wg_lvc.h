@@ -17,6 +17,8 @@
 //   wg_lvc_forward       one workgroup per (item, frame): z[2D, L] = W_f[2D, R K] . X_unfold[R K, L] with the gate in the
 //                        epilogue.  W_f is read exactly once, in 24-column slices staged in LDS (coalesced rows of
 //                        the frame's contiguous [2D][R][K] block); the unfolded window is staged next to it.
+//   lvc_layer_kernel     a whole NonCausalLayerLVC of an eval pass in one launch: the same K walk, the gate tile kept in LDS, W_o,
+//                        residual and skip in the same workgroup (launched from wg_mgflow.h: wg_mg_forward / wg_mg_inverse)
 //   wg_lvc_backward_*    dX as a gather (each output column sums its K taps, each tap under the kernel of the frame it came
 //                        from: at most two frames per tap and tile, staged in LDS), so overlapping windows add without atomics;
 //                        dW_f = dz_f . X_unfold_f^T per (item, frame, 32-row slice).
@@ -48,7 +50,20 @@ struct GemmArgs {
     float *C;
     int splits, kc;      // K cut in `splits` slices of kc (a multiple of MG_BK); splits > 1: raw partials to ws[s][batch][M][N]
     float *ws;
+    // gemm_kernel<true> (the eval predictor, wg_mgflow.h): C = tanh(BatchNorm(A B)) (+ bn_res at C's offsets) with the packed running
+    // statistics of channel bat * M + m; never with a K cut
+    const double *bn_mean, *bn_invstd;
+    const float *bn_gamma, *bn_beta, *bn_res;
 };
+
+// BatchNorm1d + tanh of one value of channel c from double statistics: the arithmetic of bn_tanh_kernel and of gemm_kernel<true>
+__device__ inline float bn_tanh_value(float x, double mean, double invstd, const float *gamma, const float *beta, int c)
+{
+    float v = (float)(((double)x - mean) * invstd);
+    if (gamma) v *= gamma[c];
+    if (beta) v += beta[c];
+    return tanhf(v);
+}
 
 // split-K: how many K slices a product is cut into (1 = none).  Only a product whose tiles leave most of the chip idle and whose
 // K is long (the weight gradients: 48 x 48 outputs over 22 016 columns) is cut; each slice is at least 512 deep.
@@ -62,6 +77,7 @@ inline int gemm_splits(const wg_mg_gemm_desc &d)
     return (int)std::max<long long>(s, 1);
 }
 
+template <bool BN = false>
 __global__ __launch_bounds__(256) void gemm_kernel(GemmArgs p)
 {
     __shared__ float As[MG_BK][MG_BM + 4];
@@ -131,6 +147,11 @@ __global__ __launch_bounds__(256) void gemm_kernel(GemmArgs p)
             const long long off = bat * d.c_b + (long long)m * d.c_m + (long long)(n % d.N1) * d.c_n + (long long)(n / d.N1) * d.c_n2;
             float v = d.alpha * acc[i][j];
             if (p.D) v += d.beta * p.D[off];
+            if (BN) {
+                const int c = (int)bat * d.M + m;
+                v = bn_tanh_value(v, p.bn_mean[c], p.bn_invstd[c], p.bn_gamma, p.bn_beta, c);
+                if (p.bn_res) v += p.bn_res[off];
+            }
             p.C[off] = v;
         }
     }
@@ -214,10 +235,7 @@ __global__ __launch_bounds__(256) void bn_tanh_kernel(const float *x, long long 
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
     if (i >= total) return;
     const int c = (int)(i / N);
-    float v = (float)(((double)x[i] - mean[c]) * invstd[c]);
-    if (gamma) v *= gamma[c];
-    if (beta) v += beta[c];
-    const float t = tanhf(v);
+    const float t = bn_tanh_value(x[i], mean[c], invstd[c], gamma, beta, c);
     s[i] = t;
     if (res) sum[i] = t + res[i];
 }
@@ -300,16 +318,14 @@ struct LvcArgs {
     int R, D, K, dil, L, T, F;
 };
 
-// forward: grid (F, B); z[b][o][fL + t] = sum_j W_{b,f}[o][j] X_unfold[j][t], j = ci K + k, X_unfold[j][t] = x[b][ci][fL + t + (k - K/2) dil]
-__global__ __launch_bounds__(256) void lvc_fwd_kernel(LvcArgs a, const float *x, const float *W, float *z, float *gate)
+// The K walk of the forward for frame f of one item: W_f in LVC_JC-column slices and the unfolded window next to it, both staged in LDS;
+// thread tid accumulates the two gate rows (c, c + D) of its items tid + 256 i = c L + t.
+//   z[b][o][fL + t] = sum_j W_{b,f}[o][j] X_unfold[j][t], j = ci K + k, X_unfold[j][t] = x[b][ci][fL + t + (k - K/2) dil]
+__device__ __forceinline__ void lvc_walk(const LvcArgs &a, const float *xb, const float *Wf, int f, float (*Ws)[LVC_JC + 1],
+                                         float (*Xs)[LVC_MAXL], float (&aw)[LVC_ITEMS], float (&av)[LVC_ITEMS])
 {
-    __shared__ float Ws[2 * LVC_MAXD][LVC_JC + 1];
-    __shared__ float Xs[LVC_JC][LVC_MAXL];
-    const int f = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
+    const int tid = threadIdx.x;
     const int RK = a.R * a.K, D2 = 2 * a.D, half = (a.K - 1) / 2, nitems = a.D * a.L;
-    const float *Wf = W + ((long long)b * a.F + f) * ((long long)D2 * RK);
-    const float *xb = x + (long long)b * a.R * a.T;
-    float aw[LVC_ITEMS], av[LVC_ITEMS];
 #pragma unroll
     for (int i = 0; i < LVC_ITEMS; ++i) aw[i] = av[i] = 0.f;
     for (int j0 = 0; j0 < RK; j0 += LVC_JC) {
@@ -346,6 +362,17 @@ __global__ __launch_bounds__(256) void lvc_fwd_kernel(LvcArgs a, const float *x,
             }
         }
     }
+}
+
+// forward: grid (F, B); z and the gate of frame f of item b
+__global__ __launch_bounds__(256) void lvc_fwd_kernel(LvcArgs a, const float *x, const float *W, float *z, float *gate)
+{
+    __shared__ float Ws[2 * LVC_MAXD][LVC_JC + 1];
+    __shared__ float Xs[LVC_JC][LVC_MAXL];
+    const int f = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
+    const int D2 = 2 * a.D, nitems = a.D * a.L;
+    float aw[LVC_ITEMS], av[LVC_ITEMS];
+    lvc_walk(a, x + (long long)b * a.R * a.T, W + ((long long)b * a.F + f) * ((long long)D2 * a.R * a.K), f, Ws, Xs, aw, av);
 #pragma unroll
     for (int i = 0; i < LVC_ITEMS; ++i) {
         const int item = tid + i * 256;
@@ -355,6 +382,78 @@ __global__ __launch_bounds__(256) void lvc_fwd_kernel(LvcArgs a, const float *x,
             z[((long long)b * D2 + c) * a.T + col] = aw[i];
             z[((long long)b * D2 + c + a.D) * a.T + col] = av[i];
             gate[((long long)b * a.D + c) * a.T + col] = tanhf(aw[i]) * sigmoidf_(av[i]);
+        }
+    }
+}
+
+// One NonCausalLayerLVC of an eval pass in one launch (wg_mg_forward / wg_mg_inverse): grid (F, B) as lvc_fwd_kernel and the same K
+// walk; the frame's gate tile [D][L] stays in LDS, W_o . gate runs in the same workgroup, and neither z nor the gate reaches memory.
+//   hn[b][r][fL + t]   = h[b][r][fL + t] + sum_d wo[r][d] gate[d][t]            (r < R; absent in the last layer)
+//   skip[b][s][fL + t] (+)= sum_d wo[R + s][d] gate[d][t]                       (the first layer stores, later layers add in place)
+// hn is the OTHER of two planes: the neighbouring frames' workgroups still read this frame's columns of h as their halo.  The
+// workgroup owns its L columns of hn and skip.  After the walk its two LDS arrays are free: the gate tile takes the window's
+// (D L <= 2048 floats of its 3072) and W_o is staged in the kernel slices' (LVC_WO_FLOATS / D rows at a time), so the launch needs
+// no more LDS than lvc_fwd_kernel and four workgroups share a CU.
+struct LvcLayerArgs {
+    LvcArgs a;
+    int S, first, last;
+    const float *h, *W, *wo;
+    float *hn, *skip;
+};
+#define LVC_WO_FLOATS (2 * LVC_MAXD * (LVC_JC + 1))
+
+__global__ __launch_bounds__(256) void lvc_layer_kernel(LvcLayerArgs p)
+{
+    __shared__ float Ws[2 * LVC_MAXD][LVC_JC + 1];
+    __shared__ float Xs[LVC_JC][LVC_MAXL];
+    static_assert(LVC_JC * LVC_MAXL >= 256 * LVC_ITEMS, "the gate tile must fit the window's array");
+    const LvcArgs &a = p.a;
+    const int f = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
+    const int nitems = a.D * a.L;
+    float aw[LVC_ITEMS], av[LVC_ITEMS];
+    lvc_walk(a, p.h + (long long)b * a.R * a.T, p.W + ((long long)b * a.F + f) * ((long long)2 * a.D * a.R * a.K), f, Ws, Xs, aw, av);
+    float *Gs = &Xs[0][0], *Wo = &Ws[0][0];
+    __syncthreads();                                                             // the last slice has been read by everyone
+#pragma unroll
+    for (int i = 0; i < LVC_ITEMS; ++i) {
+        const int item = tid + i * 256;
+        if (item < nitems) Gs[item] = tanhf(aw[i]) * sigmoidf_(av[i]);          // Gs[c L + t]
+    }
+    const int nres = p.last ? 0 : a.R, nrows = nres + p.S, chunk = LVC_WO_FLOATS / a.D;
+    for (int r0 = 0; r0 < nrows; r0 += chunk) {
+        const int rn = min(chunk, nrows - r0);
+        __syncthreads();                                                         // the gate tile is written; the previous rows are used up
+        for (int idx = tid; idx < rn * a.D; idx += 256) Wo[idx] = p.wo[(long long)r0 * a.D + idx];
+        __syncthreads();
+        // four outputs per thread at a time: four independent fma chains (each over d ascending) hide the LDS latency
+        for (int item0 = tid; item0 < rn * a.L; item0 += 4 * 256) {
+            int wrow[4], t[4];
+            float s[4];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const int item = min(item0 + q * 256, rn * a.L - 1);             // (a slot past the end recomputes the last output, unused)
+                wrow[q] = item / a.L * a.D;
+                t[q] = item % a.L;
+                s[q] = 0.f;
+            }
+            for (int d = 0; d < a.D; ++d) {
+#pragma unroll
+                for (int q = 0; q < 4; ++q) s[q] = fmaf(Wo[wrow[q] + d], Gs[d * a.L + t[q]], s[q]);
+            }
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const int item = item0 + q * 256;
+                if (item >= rn * a.L) break;
+                const int r = r0 + item / a.L;
+                const long long col = (long long)f * a.L + t[q];
+                if (r < nres) {
+                    const long long off = ((long long)b * a.R + r) * a.T + col;
+                    p.hn[off] = s[q] + p.h[off];
+                } else {
+                    const long long off = ((long long)b * p.S + (r - nres)) * a.T + col;
+                    p.skip[off] = p.first ? s[q] : s[q] + p.skip[off];
+                }
+            }
         }
     }
 }
@@ -482,12 +581,13 @@ int wg_mg_gemm(const wg_mg_gemm_desc *d, const float *A, const float *B, const f
     if (gy > 65535 || d->batch > 65535 || gx > 0x7fffffffLL) return WG_EUNSUPPORTED;
     mg::GemmArgs p;
     p.d = *d; p.A = A; p.B = B; p.D = D; p.C = C;
+    p.bn_mean = p.bn_invstd = nullptr; p.bn_gamma = p.bn_beta = p.bn_res = nullptr;
     p.splits = mg::gemm_splits(*d);
     p.kc = (d->K + p.splits - 1) / p.splits;
     p.kc = (p.kc + MG_BK - 1) / MG_BK * MG_BK;
     p.ws = (float *)ws;
     if (p.splits > 1 && (!ws || ws_bytes < wg_mg_gemm_workspace_bytes(d))) return WG_EWORKSPACE;
-    hipLaunchKernelGGL(mg::gemm_kernel, dim3((unsigned)gx, (unsigned)gy, (unsigned)(d->batch * p.splits)), dim3(256), 0,
+    hipLaunchKernelGGL(mg::gemm_kernel<false>, dim3((unsigned)gx, (unsigned)gy, (unsigned)(d->batch * p.splits)), dim3(256), 0,
                        (hipStream_t)stream, p);
     if (p.splits > 1) {
         if (hipGetLastError() != hipSuccess) return WG_ELAUNCH;

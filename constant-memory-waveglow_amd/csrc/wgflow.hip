@@ -4143,3 +4143,5 @@ int wg_coupling_backward(const wg_wn_dims *dd, const void *const *params, const 
 }
 
 }  // extern "C"
+
+#include "wg_mgflow.h"      // MelGlow's eval passes: uses the 1x1's launchers above and the kernels of wg_lvc.h

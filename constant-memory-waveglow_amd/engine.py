@@ -142,10 +142,60 @@ class PackedWeights:
         self.key = self._pending
 
 
-class ModelEngine:
+class _InverseGraphs:
+    """The WG_GRAPHS / auto-capture policy of a model's synthesis call, shared by the engines that have one (ModelEngine, MelGlowEngine).
+    `launch(z, h) -> (out, logdet)` enqueues the whole call on the current stream and allocates its two outputs."""
+
+    def __init__(self):
+        self._graphs = {}                        # (device, shape, frames, packed buffer, workspace) -> captured inverse (hipGraph)
+        self._graph_seen = {}                    # auto mode: how often a small call's key has occurred
+
+    def _run_inverse(self, key, launch, z, h):
+        """Direct launches, or (see _graph_mode) the captured call replayed."""
+        mode = _graph_mode()
+        if mode != "0" and not torch.cuda.is_current_stream_capturing():
+            if mode == "1" or key in self._graphs:
+                return self._replay_inverse(key, launch, z, h)
+            if z.numel() <= 65536:                          # auto: capture a small call on its third occurrence
+                n = self._graph_seen.get(key, 0) + 1
+                if len(self._graph_seen) > 16:
+                    self._graph_seen.clear()
+                self._graph_seen[key] = n
+                if n >= 3:
+                    try:
+                        return self._replay_inverse(key, launch, z, h)
+                    except Exception:                       # noqa: BLE001 -- a capture that fails only costs the graph: direct launches go on
+                        self._graph_seen[key] = -(1 << 30)
+        return launch(z, h)
+
+    def _replay_inverse(self, key, launch, z, h):
+        """The whole inverse call (~250 launches) captured once per shape into a hipGraph (torch.cuda.CUDAGraph on the stream the C ABI
+        enqueues on) and replayed; the packed weights and the workspace are referenced by address, so a re-pack in place is seen."""
+        ent = self._graphs.get(key)
+        if ent is None:
+            sz, sh = z.clone(), h.clone()
+            launch(sz, sh)                                          # warm-up outside capture
+            torch.cuda.synchronize()
+            graph = torch.cuda.CUDAGraph()
+            # thread_local: only THIS thread's calls are illegal during the capture -- another thread of the process (a serving thread,
+            # an nn.DataParallel replica sharing this engine) that allocates or launches meanwhile is left alone; one capture at a time
+            with _CAPTURE_LOCK, torch.cuda.graph(graph, capture_error_mode="thread_local"):
+                out, logdet = launch(sz, sh)
+            while len(self._graphs) >= 4:
+                self._graphs.pop(next(iter(self._graphs)))
+            ent = self._graphs[key] = (graph, sz, sh, out, logdet)
+        graph, sz, sh, out, logdet = ent
+        sz.copy_(z)
+        sh.copy_(h)
+        graph.replay()
+        return out.clone(), logdet.clone()
+
+
+class ModelEngine(_InverseGraphs):
     """Whole-model entry points (wg_pack_weights / wg_forward / wg_inverse / wg_backward)."""
 
     def __init__(self, cfg: WgConfig):
+        super().__init__()
         self.cfg = cfg
         self.cfg_keep = WgConfig.from_buffer_copy(cfg)      # the same model in stored-activation mode (memory_efficient=False)
         self.cfg_keep.keep_activations = 1
@@ -153,8 +203,6 @@ class ModelEngine:
         self.buffers = _Buffers()
         self.packed = PackedWeights()
         self.n_params = None
-        self._graphs = {}                        # (device, shape, frames, packed buffer, workspace) -> captured inverse (hipGraph)
-        self._graph_seen = {}                    # auto mode: how often a small call's key has occurred
 
     def _pack(self, params, device):
         L = _lib.lib()
@@ -211,44 +259,10 @@ class ModelEngine:
         B, N = x.shape
         pk = self._pack(params, x.device)
         ws = self._ws(B, N, 0, x.device)
-        mode = _graph_mode() if inverse else "0"
-        if mode != "0" and not torch.cuda.is_current_stream_capturing():
+        if inverse:
             key = (x.device, tuple(x.shape), h.shape[2], pk.data_ptr(), ws.data_ptr())
-            if mode == "1" or key in self._graphs:
-                return self._replay_inverse(key, pk, ws, x, h)
-            if x.numel() <= 65536:                          # auto: capture a small call on its third occurrence
-                n = self._graph_seen.get(key, 0) + 1
-                if len(self._graph_seen) > 16:
-                    self._graph_seen.clear()
-                self._graph_seen[key] = n
-                if n >= 3:
-                    try:
-                        return self._replay_inverse(key, pk, ws, x, h)
-                    except Exception:                       # noqa: BLE001 -- a capture that fails only costs the graph: direct launches go on
-                        self._graph_seen[key] = -(1 << 30)
-        return self._launch(pk, ws, x, h, inverse)
-
-    def _replay_inverse(self, key, pk, ws, z, h):
-        """The whole wg_inverse call (~250 launches) captured once per shape into a hipGraph (torch.cuda.CUDAGraph on the stream the C ABI
-        enqueues on) and replayed; the packed weights and the workspace are referenced by address, so a re-pack in place is seen."""
-        ent = self._graphs.get(key)
-        if ent is None:
-            sz, sh = z.clone(), h.clone()
-            self._launch(pk, ws, sz, sh, True)                      # warm-up outside capture
-            torch.cuda.synchronize()
-            graph = torch.cuda.CUDAGraph()
-            # thread_local: only THIS thread's calls are illegal during the capture -- another thread of the process (a serving thread,
-            # an nn.DataParallel replica sharing this engine) that allocates or launches meanwhile is left alone; one capture at a time
-            with _CAPTURE_LOCK, torch.cuda.graph(graph, capture_error_mode="thread_local"):
-                out, logdet = self._launch(pk, ws, sz, sh, True)
-            while len(self._graphs) >= 4:
-                self._graphs.pop(next(iter(self._graphs)))
-            ent = self._graphs[key] = (graph, sz, sh, out, logdet)
-        graph, sz, sh, out, logdet = ent
-        sz.copy_(z)
-        sh.copy_(h)
-        graph.replay()
-        return out.clone(), logdet.clone()
+            return self._run_inverse(key, lambda sz, sh: self._launch(pk, ws, sz, sh, True), x, h)
+        return self._launch(pk, ws, x, h, False)
 
     @on_device
     def backward(self, params, z, h, dz, dlogdet, need, need_dh, need_dx, want_x=False, grads_out=None, flow_events=None,
@@ -910,6 +924,91 @@ def lvc_gate_backward(z, dgate):
     dz = torch.empty_like(z)
     check(_lib.lib().wg_lvc_gate_backward(_p(z), _p(dgate), Bn, D, T, _p(dz), _stream(z.device)), "wg_lvc_gate_backward")
     return dz
+
+
+# ---- MelGlow's eval passes (include/wgflow.h wg_mg_check .. wg_mg_inverse; csrc/wg_mgflow.h) ------------------------------------------
+class MelGlowEngine(_InverseGraphs):
+    """Model-level, no-autograd passes of MelGlow in eval(): wg_mg_pack_weights once per weight change, then wg_mg_forward /
+    wg_mg_inverse from the packed weights and one workspace.  `table`: the model's float state-dict tensors in the header's order."""
+
+    def __init__(self, cfg):
+        super().__init__()
+        self.cfg = cfg
+        self.buffers = _Buffers()
+        self.packed = PackedWeights()
+        self._eps = None
+
+    def check(self, B, N, F):
+        """0, or the library's error code for a shape the passes do not serve (no launch, no device needed)."""
+        return _lib.lib().wg_mg_check(C.byref(self.cfg), B, N, F)
+
+    def _pack(self, table, eps, device):
+        L = _lib.lib()
+        if len(table) != L.wg_mg_param_count(C.byref(self.cfg)):
+            raise WgError("MelGlow parameter table has %d entries, expected %d" % (len(table), L.wg_mg_param_count(C.byref(self.cfg))))
+        eps = tuple(float(e) for e in eps)
+        if self.packed.stale(table) or self.packed.buf.device != device or eps != self._eps:
+            require_device(*table)
+            nbytes = L.wg_mg_packed_bytes(C.byref(self.cfg))
+            if nbytes == 0:
+                raise WgError("MelGlow configuration not supported by the one-call passes (include/wgflow.h wg_mg_check)")
+            if self.packed.buf is None or self.packed.buf.numel() < nbytes or self.packed.buf.device != device:
+                self.packed.buf = torch.empty(nbytes, dtype=torch.uint8, device=device)
+            check(L.wg_mg_pack_weights(C.byref(self.cfg), _table([t.contiguous() if t is not None else None for t in table]),
+                                       (C.c_float * len(eps))(*eps), _p(self.packed.buf), _stream()), "wg_mg_pack_weights")
+            self.packed.commit()
+            self._eps = eps
+        return self.packed.buf
+
+    def _launch(self, pk, ws, x, h, inverse):
+        B, N = x.shape
+        out = torch.empty_like(x)
+        logdet = torch.empty(B, dtype=torch.float32, device=x.device)
+        fn = _lib.lib().wg_mg_inverse if inverse else _lib.lib().wg_mg_forward
+        check(fn(C.byref(self.cfg), _p(pk), _p(x), _p(h), B, N, h.shape[2], _p(out), _p(logdet), _p(ws), ws.numel(), _stream()),
+              "wg_mg_inverse" if inverse else "wg_mg_forward")
+        return out, logdet
+
+    @on_device
+    def run(self, x, h, table, eps, inverse, synthesis):
+        """x [B, N] (N a multiple of the hop), h [B, n_mels, F >= N / hop]; inverse: reverse_computation.  synthesis: this is the
+        direction towards the audio, which may be replayed from a captured graph (WG_GRAPHS, as ModelEngine.run)."""
+        require_device(x, h)
+        x, h = x.contiguous(), h.contiguous()
+        B, N = x.shape
+        pk = self._pack(table, eps, x.device)
+        nbytes = _lib.lib().wg_mg_workspace_bytes(C.byref(self.cfg), B, N)
+        ws = self.buffers.get((x.device, B, N), nbytes, x.device)
+        if synthesis:
+            key = (x.device, tuple(x.shape), h.shape[2], pk.data_ptr(), ws.data_ptr(), bool(inverse))
+            return self._run_inverse(key, lambda sz, sh: self._launch(pk, ws, sz, sh, inverse), x, h)
+        return self._launch(pk, ws, x, h, inverse)
+
+    @on_device
+    def predictor(self, h, table, eps, flow, frames=None):
+        """Predictor.forward in eval() of flow `flow` through the passes' own launches: h [B, n_mels, F] -> [depth, B frames, 2D R radix]."""
+        require_device(h)
+        h = h.contiguous()
+        B, _, F = h.shape
+        Fr = F if frames is None else frames
+        c = self.cfg
+        pk = self._pack(table, eps, h.device)
+        plane = (c.pred_ch * c.depth * B * Fr + 3) // 4 * 4
+        ws = torch.empty(3 * plane, dtype=torch.float32, device=h.device)
+        out = torch.empty((c.depth, B * Fr, 2 * c.dil_ch * c.res_ch * c.radix), dtype=torch.float32, device=h.device)
+        check(_lib.lib().wg_mg_predictor_apply(C.byref(c), _p(pk), flow, _p(h), B, Fr, F, _p(out), _p(ws), ws.numel() * 4, _stream()),
+              "wg_mg_predictor_apply")
+        return out
+
+
+def mg_layer_apply(dims, skip_ch, h, w, wo, F, skip, first, last):
+    """One NonCausalLayerLVC in one launch (wg_mg_layer_apply): h [B, R, T], w [B, F, 2D, R, radix], wo the effective W_o [rows, D] ->
+    (h + res in a new tensor, or None when last; skip stored (first) or added to in place)."""
+    Bn, R, T = h.shape
+    hn = None if last else torch.empty_like(h)
+    check(_lib.lib().wg_mg_layer_apply(C.byref(dims), skip_ch, int(first), int(last), _p(h), _p(w), _p(wo), Bn, T, F, _p(hn), _p(skip),
+                                       _stream(h.device)), "wg_mg_layer_apply")
+    return hn, skip
 
 
 # ---- MRWaveGlow's plumbing (csrc/wg_mr.h): one launch each, the caller's tensors in and out -------------------------------------------

@@ -12,10 +12,15 @@ define `hip_dims`, so AffineCouplingBlock runs it through its generic path: no g
 backward -- and with it the reference's BatchNorm semantics: in train() every call of the transform moves the running statistics
 (twice per step when memory-efficient, once otherwise; also in `infer`, which does not switch to eval()).
 
+In eval() with autograd disabled a whole pass is ONE library call instead (MelGlow._engine_pass: wg_mg_forward / wg_mg_inverse from
+packed weights, csrc/wg_mgflow.h); everything else -- train(), grad enabled, the modules on their own -- stays on the path above.
+
 Layout.  The predictor's activations are [channels, B * frames] (column n = b F + f), read from and written to the callers' [B, C, F]
 tensors by the products' strides.  Inside WN_LVC the predicted kernels are [depth][B * F][2D R radix] (each frame's kernel contiguous,
 what the LVC kernels read); the stand-alone Predictor returns the reference's [B, depth * M, F].
 """
+import os
+import weakref
 from typing import Tuple
 
 import torch
@@ -23,10 +28,10 @@ from torch import Tensor, nn
 from torch.autograd import Function
 
 from . import engine
-from ._lib import WgError, WgLvcDims
+from ._lib import WgError, WgLvcDims, WgMgConfig
 from .base import FlowBase
 from .efficient_modules import AffineCouplingBlock, InvertibleConv1x1
-from .utils import add_weight_norms, conv_gv
+from .utils import SlotTable, add_weight_norms, conv_gv, conv_gv_slots
 
 __all__ = ["Predictor", "NonCausalLayerLVC", "WN_LVC", "MelGlow"]
 
@@ -401,6 +406,9 @@ class WN_LVC(nn.Module):
 
 
 # ---- MelGlow --------------------------------------------------------------------------------------------------------------------
+_ENGINES = weakref.WeakKeyDictionary()      # model -> engine.MelGlowEngine (packed weights, workspaces, graphs): not part of the module's state
+
+
 class MelGlow(FlowBase):
     """WaveGlow's flow stack with WN_LVC couplings, conditioned on the mel frames without upsampling (melglow.py:162-258 upstream)."""
 
@@ -426,6 +434,84 @@ class MelGlow(FlowBase):
             self.WNs.append(AffineCouplingBlock(WN_LVC, memory_efficient=memory_efficient, reverse_mode=reverse_mode,
                                                 in_channels=c // 2, aux_channels=n_mels, **kwargs))
         self.z_split_sizes.append(c)
+        self._mg_table = SlotTable("mg_slots")
+
+    # -- the one-call eval passes (include/wgflow.h wg_mg_*) ---------------------------------------------------------------------------
+    def mg_slots(self):
+        """Where every entry of the C ABI's table lives in the module tree: state_dict() order, float tensors only (parameters and
+        BatchNorm running statistics), a conv's (weight_g, weight_v) pair as (None, weight) once weight norm was removed."""
+        def bn(m):
+            return [(m._parameters, "weight"), (m._parameters, "bias"), (m._buffers, "running_mean"), (m._buffers, "running_var")]
+
+        slots = [(m._parameters, "weight") for m in self.invconv1x1]
+        for blk in self.WNs:
+            wn = blk.F
+            slots += list(conv_gv_slots(wn.start))
+            for layer in wn.layers:
+                slots += list(conv_gv_slots(layer.W_o))
+            slots.append((wn.end._parameters, "weight"))
+            pred = wn.pred
+            slots += [(pred.start[0]._parameters, "weight")] + bn(pred.start[1]) + [(pred.end._parameters, "weight")]
+            for rb in pred.res_blocks:
+                slots += [(rb[0]._parameters, "weight")] + bn(rb[1]) + [(rb[3]._parameters, "weight")] + bn(rb[4])
+        return slots
+
+    def mg_table(self):
+        return self._mg_table(self)
+
+    def mg_config(self):
+        wn = self.WNs[0].F
+        return WgMgConfig(self.flows, self.n_group, self.n_early_every, self.n_early_size, self._hop_length, self.n_mels, len(wn.layers),
+                          wn.res_chs, wn.dil_chs, wn.skp_chs, wn.rdx, wn.pred.start[0].out_channels // wn.pred.groups,
+                          len(wn.pred.res_blocks), int(self._reverse_mode))
+
+    def mg_engine(self):
+        eng = _ENGINES.get(self)
+        if eng is None:
+            eng = _ENGINES[self] = engine.MelGlowEngine(self.mg_config())
+        return eng
+
+    def _engine_route(self, x, h):
+        """(None, table, eps) when this call goes through the one-call engine, else (why not, None, None): the module path runs.  The
+        engine serves exactly: autograd disabled, every module in eval(), every BatchNorm with running statistics and affine parameters,
+        no conv bias, CUDA float32 tensors, a shape wg_mg_check accepts, and WG_MG_ENGINE (read per call) not "0"."""
+        if os.environ.get("WG_MG_ENGINE") == "0":
+            return "WG_MG_ENGINE=0", None, None
+        if torch.is_grad_enabled():
+            return "autograd is enabled", None, None
+        eps = []
+        for m in self.modules():
+            if m.training:
+                return "a module is in train()", None, None
+            if isinstance(m, nn.BatchNorm1d):
+                eps.append(m.eps)
+            elif isinstance(m, nn.Conv1d) and m.bias is not None:
+                return "bias=True", None, None
+        if x.dim() != 2 or h.dim() != 3 or x.size(0) != h.size(0) or h.size(1) != self.n_mels:
+            return "not audio [B, N] with conditioning [B, n_mels, frames]", None, None
+        table = self.mg_table()
+        for i, t in enumerate(table):
+            if t is None:
+                if i < self.flows or (i - self.flows) % (len(table) // self.flows - 1) >= 2 + 2 * len(self.WNs[0].F.layers):
+                    return "a BatchNorm without running statistics or affine parameters", None, None
+            elif t.dtype != torch.float32:
+                return "parameters are not float32", None, None
+        N = x.size(1) // self._hop_length * self._hop_length
+        rc = self.mg_engine().check(x.size(0), N, h.size(2)) if N else -2
+        if rc:
+            return "wg_mg_check: code %d" % rc, None, None
+        if not (x.is_cuda and x.dtype == torch.float32 and h.dtype == torch.float32 and h.device == x.device and table[0].device == x.device):
+            return "tensors are not float32 on one HIP device", None, None
+        return None, table, eps
+
+    def _engine_pass(self, x, h, inverse):
+        """forward_computation / reverse_computation as one library call (wg_mg_forward / wg_mg_inverse), or None: the module path runs.
+        The caller's tensors are only read."""
+        why, table, eps = self._engine_route(x, h)
+        if why is not None:
+            return None
+        N = x.size(1) // self._hop_length * self._hop_length
+        return self.mg_engine().run(x[:, :N], h, [t.detach() for t in table], eps, inverse, synthesis=inverse != self._reverse_mode)
 
     def _frames(self, x, h):
         """x [B, N] -> [B, n_group, T] (N cut to whole hops) and the T / upsample_factor mel frames it is conditioned on."""
@@ -437,6 +523,9 @@ class MelGlow(FlowBase):
         return x, h[..., :x.shape[2] // self.upsample_factor]
 
     def forward_computation(self, x: Tensor, h: Tensor) -> Tuple[Tensor, Tensor]:
+        out = self._engine_pass(x, h, False)
+        if out is not None:
+            return out
         B = x.size(0)
         x, y = self._frames(x, h)
         early = []
@@ -456,6 +545,9 @@ class MelGlow(FlowBase):
         return torch.cat([o.transpose(1, 2) for o in early], 2).view(B, -1), logdet
 
     def reverse_computation(self, z: Tensor, h: Tensor) -> Tuple[Tensor, Tensor]:
+        out = self._engine_pass(z, h, True)
+        if out is not None:
+            return out
         B = z.size(0)
         z, y = self._frames(z, h)
         parts = z.split(self.z_split_sizes, 1)

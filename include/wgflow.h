@@ -458,6 +458,74 @@ int wg_mr_upsample_backward(const float *dout, int rows, int r0, int B, int n_me
 int wg_mr_pack(const float *src, int B, int c, int T, int n_group, int off, float *dst, void *stream);
 int wg_mr_unpack(const float *src, int B, int c, int T, int n_group, int off, float *dst, void *stream);
 
+/* ---- MelGlow, model level: the eval-mode passes (model/melglow.py:196-258 upstream with every module in eval()) ------------------
+ * Appended to revision 10 without changing any earlier declaration (purely additive: the revision stays 10).  What wg_forward /
+ * wg_inverse are to WaveGlow: MelGlow.forward_computation / reverse_computation as ONE call each, from weights packed once per
+ * weight change and one workspace.  No autograd counterpart: the training step stays composed from the building blocks above.
+ * Exact fp32 on the vector ALUs (the result does not depend on WG_PREC_*), every reduction in a fixed order: two runs give the same bits.
+ *
+ * wg_mg_config: the arguments of MelGlow(...) and the WN_LVC keyword arguments it forwards.  A frame owns L = hop / n_group columns.
+ * reverse_mode: MelGlow(reverse_mode=True) builds every block with the switch set (base.py:20-28), so forward_computation then walks the
+ * flows first to last with each block's z -> x arithmetic and reverse_computation last to first with the x -> z arithmetic.
+ *
+ * Table ("table" of wg_mg_pack_weights): device pointers in the order of the model's state_dict() restricted to its float tensors
+ * (parameters and BatchNorm running_mean / running_var; num_batches_tracked is skipped), wg_mg_param_count entries:
+ *     [0 .. flows)                  invconv1x1.{k}.weight [c_k, c_k, 1]
+ *     then per flow k (WNs.{k}.F.), 9 + 2 depth + 10 pred_layers entries:
+ *         start.weight_g, start.weight_v [res_ch, c_k / 2, 1]
+ *         layers.{i}.W_o.weight_g, layers.{i}.W_o.weight_v [res_ch + skip_ch (skip_ch in the last layer), dil_ch, 1]   (i = 0 .. depth-1)
+ *         end.weight [c_k, skip_ch, 1]
+ *         pred.start.0.weight [H G, n_mels, 1], pred.start.1.{weight, bias, running_mean, running_var} [H G]   (H = pred_ch, G = depth)
+ *         pred.end.weight [2 dil_ch res_ch radix G, H, 1]
+ *         pred.res_blocks.{r}.0.weight [H G, H, 1], .1.{weight, bias, running_mean, running_var},
+ *         pred.res_blocks.{r}.3.weight [H G, H, 1], .4.{weight, bias, running_mean, running_var}                      (r = 0 .. pred_layers-1)
+ * A NULL weight_g means the conv carries a plain weight in its weight_v slot (as `params` of wg_layer_apply); nothing else may be NULL.
+ * bn_eps (host, nullable = 1e-5 everywhere): flows x (1 + 2 pred_layers) values, the eps of every BatchNorm in table order.
+ *
+ * pack_weights (once per weight change, not per call): the weight-normed start and W_o, every BatchNorm's running mean and
+ * 1 / sqrt(var + eps) as double[C] (what wg_mg_bn_stats(train = 0) produces) next to its weight / bias, and per 1x1 what
+ * wg_invconv_apply needs in both directions: W, W^-1, log|det W| (NaN for a negative determinant).
+ *
+ * forward / inverse: audio (z) [B, N] read as [B, T, n_group], N % hop == 0 or WG_ESHAPE; h [B, n_mels, F] with F >= N / hop, only its
+ * first N / hop frames read (through the stride F); early outputs leave and re-enter at the channel offsets of z_split_sizes;
+ * logdet[B] = sum over flows of (+-) T log|det W| + the per-item sum of log_s.  The input is not modified.  Everything is enqueued on
+ * `stream` in one linear chain: no allocation, no synchronisation, no read-back, so the call can be captured into a graph.
+ *
+ * check: WG_OK, or why the passes do not serve the shape, before anything is launched: everything outside wg_lvc_check's limits for
+ * the layers' dilations 1 .. 2^(depth-1), more than 64 flows, depth > 16, n_group > 32, a flow with an odd number of channels, hop not a
+ * multiple of n_group, skip_ch or pred_ch > 4096, n_mels > 65536, pred_layers > 64, B * (N / hop) > 65535 * 64, n_mels * F or B * N
+ * past 2^31 - 1 (WG_EUNSUPPORTED); N % hop or F < N / hop (WG_ESHAPE).
+ * workspace_bytes / packed_bytes / param_count return 0 for a configuration (or shape) the check refuses. */
+typedef struct wg_mg_config {
+    int32_t flows, n_group, n_early_every, n_early_size, hop, n_mels;
+    int32_t depth, res_ch, dil_ch, skip_ch, radix, pred_ch, pred_layers;
+    int32_t reverse_mode;
+} wg_mg_config;
+int    wg_mg_check(const wg_mg_config *cfg, int B, int N, int F);
+int    wg_mg_param_count(const wg_mg_config *cfg);
+size_t wg_mg_packed_bytes(const wg_mg_config *cfg);
+size_t wg_mg_workspace_bytes(const wg_mg_config *cfg, int B, int N);
+int    wg_mg_pack_weights(const wg_mg_config *cfg, const void *const *table, const float *bn_eps, void *packed, void *stream);
+int    wg_mg_forward(const wg_mg_config *cfg, const void *packed, const float *audio, const float *h, int B, int N, int F,
+                     float *z, float *logdet, void *ws, size_t ws_bytes, void *stream);
+int    wg_mg_inverse(const wg_mg_config *cfg, const void *packed, const float *z, const float *h, int B, int N, int F,
+                     float *x, float *logdet, void *ws, size_t ws_bytes, void *stream);
+/* diagnostics, like the other wg_stat_*: passes run by this process, and launches of the one-launch layer kernel (lvc_layer_kernel:
+ * flows x depth per pass) */
+long long wg_stat_mg_pass_calls(void);
+long long wg_stat_mg_layer_launches(void);
+/* The two pieces of a pass on their own (what the tests measure them through).
+ * layer_apply: one NonCausalLayerLVC in one launch: h [B][res_ch][T], w [B][F][2 dil_ch][res_ch][radix] as wg_lvc_forward, wo the effective
+ *   W_o [res_ch + skip_ch (skip_ch when last)][dil_ch] -> h_next = h + res (a buffer other than h: neighbouring frames read h as their
+ *   halo; not written when last) and skip [B][skip_ch][T], stored when first, else added to in place.  Limits: wg_lvc_check.
+ * predictor_apply: Predictor.forward in eval() for flow `flow` of a packed model: h [B][n_mels][F], its first Fr frames ->
+ *   kernels [depth][B Fr][2 dil_ch res_ch radix] (each frame's kernel contiguous).  ws: 3 planes of pred_ch depth B Fr floats, each
+ *   rounded up to a multiple of 4 floats. */
+int    wg_mg_layer_apply(const wg_lvc_dims *d, int skip_ch, int first, int last, const float *h, const float *w, const float *wo,
+                         int B, int T, int F, float *h_next, float *skip, void *stream);
+int    wg_mg_predictor_apply(const wg_mg_config *cfg, const void *packed, int flow, const float *h, int B, int Fr, int F, float *kernels,
+                             void *ws, size_t ws_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
