@@ -30,6 +30,8 @@ ABI_SYMBOLS = [
     "wg_mr_haar_split", "wg_mr_haar_merge", "wg_mr_upsample", "wg_mr_upsample_backward", "wg_mr_pack", "wg_mr_unpack",
     "wg_mg_check", "wg_mg_param_count", "wg_mg_packed_bytes", "wg_mg_workspace_bytes", "wg_mg_pack_weights", "wg_mg_forward", "wg_mg_inverse",
     "wg_stat_mg_pass_calls", "wg_stat_mg_layer_launches", "wg_mg_layer_apply", "wg_mg_predictor_apply",
+    "wg_mr_check", "wg_mr_param_count", "wg_mr_packed_bytes", "wg_mr_workspace_bytes", "wg_mr_pack_weights", "wg_mr_forward", "wg_mr_inverse",
+    "wg_stat_mr_pass_calls", "wg_mr_plane_geo", "wg_mr_plane_split", "wg_mr_plane_merge", "wg_mr_plane_upsample",
 ]
 K_CONV_STORE, K_CONV_GATE, K_CONV_RESSKIP, K_CONV_DGATE, K_WGRAD, K_LAYER, K_THIN = range(7)
 
@@ -66,6 +68,11 @@ class WgLvcDims(C.Structure):
 class WgMgConfig(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("flows", "n_group", "n_early_every", "n_early_size", "hop", "n_mels", "depth", "res_ch", "dil_ch",
                                          "skip_ch", "radix", "pred_ch", "pred_layers", "reverse_mode")]
+
+
+class WgMrConfig(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("prior_flows", "flows", "levels", "n_group", "hop_size", "n_mels", "super_resolution", "reverse_mode",
+                                         "dilation_channels", "residual_channels", "skip_channels", "depth", "radix", "bias", "precision")]
 
 
 PREC_F32, PREC_BF16X3, PREC_BF16X3_PLANES = 0, 1, 2
@@ -226,6 +233,22 @@ def lib():
     L.wg_stat_mg_layer_launches.argtypes = []
     L.wg_mg_layer_apply.argtypes = [lvcp, i, i, i, vp, vp, vp, i, i, i, vp, vp, vp]
     L.wg_mg_predictor_apply.argtypes = [mgp, vp, i, vp, i, i, i, vp, vp, sz, vp]
+    mrp, ip = C.POINTER(WgMrConfig), C.POINTER(C.c_int)
+    L.wg_mr_check.argtypes = [mrp, i, i, i]
+    L.wg_mr_param_count.argtypes = [mrp]
+    L.wg_mr_packed_bytes.restype = sz
+    L.wg_mr_packed_bytes.argtypes = [mrp]
+    L.wg_mr_workspace_bytes.restype = sz
+    L.wg_mr_workspace_bytes.argtypes = [mrp, i, i]
+    L.wg_mr_pack_weights.argtypes = [mrp, vp, vp, vp]
+    L.wg_mr_forward.argtypes = [mrp, vp, vp, vp, i, i, i, vp, vp, vp, sz, vp]
+    L.wg_mr_inverse.argtypes = [mrp, vp, vp, vp, i, i, i, vp, vp, vp, sz, vp]
+    L.wg_stat_mr_pass_calls.restype = C.c_longlong
+    L.wg_stat_mr_pass_calls.argtypes = []
+    L.wg_mr_plane_geo.argtypes = [i, i, ip, ip]
+    L.wg_mr_plane_split.argtypes = [vp, vp, i, i, i, i, i, vp, i, i, vp, i, vp, i, i, vp]
+    L.wg_mr_plane_merge.argtypes = [vp, i, vp, i, i, i, i, i, i, vp, i, vp, vp]
+    L.wg_mr_plane_upsample.argtypes = [vp, i, i, i, i, i, i, i, vp, ip, ip, vp]
     _LIB = L
     return L
 

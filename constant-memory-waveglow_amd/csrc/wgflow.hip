@@ -19,6 +19,7 @@
 #include "wg_probe.h"
 #include "wg_lvc.h"
 #include "wg_mr.h"
+#include "wg_mr_planes.h"
 
 #include <algorithm>
 #include <atomic>
@@ -3084,6 +3085,387 @@ int wg_inverse(const wg_config *cf, const void *packed, const float *z, const fl
                float *x, float *logdet, void *ws, size_t ws_bytes, void *stream)
 {
     return model_run_fwd_or_inv(cf, packed, z, h, B, N, F, 1, x, logdet, ws, ws_bytes, stream);
+}
+
+// ---- MRWaveGlow, model level (wg_mr_forward / wg_mr_inverse) --------------------------------------------------------------------
+// MRWaveGlow.forward_computation / reverse_computation as ONE call: the state stays in the planes from the first kernel to the last.
+//   state plane X [B][Gp][P]: the latent's own channel order -- level l's difference at rows [off_l, off_l + c_l), the prior's average at
+//       the last c rows -- so the latent is squeeze_kernel / unsqueeze_kernel's [B, T, n_group] layout and packing is one launch;
+//   conditioning plane of level l [B][auxp_l][P]: rows [0, c_l) the level's average, rows [c_l, c_l + n_mels) the upsampled mel (none
+//       with super_resolution); the average of level l is ALSO the input of level l + 1's split (forward) and the output of level
+//       l + 1's merge (inverse), so it is written once and never copied between levels;
+//   mel plane [B][melp][P]: the prior's conditioning; every plane's S-plane image (precision 2) is made once per call.
+// Flow k of the tables (packed LU blocks, WN packs, partial slab): the prior flows first, then level 0's, level 1's, ... -- the order of
+// the model's state_dict().
+std::atomic<long long> g_mr_pass_calls{0};                   // wg_stat_mr_pass_calls
+
+struct MrDims {
+    int L, G, s, mels, sr, rm, pf, fl, nflows;
+    int c[MR_MAX_LEVELS], off[MR_MAX_LEVELS];                // level l < L - 1: channels of its difference (= of its average), its first state row
+    int c_last, off_last;                                    // the prior's channels and first state row
+    WnD base;
+    WnD level_wn(int l) const { WnD d = base; d.ic = c[l] / 2; d.aux = c[l] + (sr ? 0 : mels); return d; }
+    WnD prior_wn() const { WnD d = base; d.ic = c_last / 2; d.aux = mels; return d; }
+    WnD flow_wn(int k) const { return k < pf ? prior_wn() : level_wn((k - pf) / fl); }
+    int flow_c(int k) const { return k < pf ? c_last : c[(k - pf) / fl]; }
+};
+static int mr_cfg_check(const wg_mr_config *cf)
+{
+    if (!cf) return WG_EINVAL;
+    if (cf->levels < 1 || cf->prior_flows < 0 || cf->flows < 0 || cf->n_group < 2 || cf->hop_size < 1 || cf->n_mels < 1) return WG_EINVAL;
+    if (cf->precision < 0 || cf->precision > 2) return WG_EINVAL;
+    if (cf->levels >= MR_MAX_LEVELS || cf->n_group > WG_MAXC) return WG_EUNSUPPORTED;      // (the 1x1 mixes at most 32 channels: at most 5 levels)
+    // MRWaveGlow.__init__: n_group halves levels - 1 times into an even channel count, and a frame owns at least one column
+    if (cf->n_group % (1 << (cf->levels - 1)) || ((cf->n_group >> (cf->levels - 1)) & 1) || cf->hop_size / cf->n_group < 1) return WG_EINVAL;
+    const long long nflows = (long long)cf->prior_flows + (long long)(cf->levels - 1) * cf->flows;
+    if (nflows < 1 || nflows > WG_MAX_FLOWS) return WG_EUNSUPPORTED;      // (no flow at all: the module returns the integer 0 as logdet)
+    return WG_OK;
+}
+static MrDims mr_dims(const wg_mr_config *cf)
+{
+    MrDims D;
+    D.L = cf->levels; D.G = cf->n_group; D.s = cf->hop_size / cf->n_group; D.mels = cf->n_mels; D.sr = cf->super_resolution != 0;
+    D.rm = cf->reverse_mode != 0; D.pf = cf->prior_flows; D.fl = D.L > 1 ? cf->flows : 0; D.nflows = D.pf + (D.L - 1) * D.fl;
+    int c = D.G, off = 0;
+    for (int l = 0; l < D.L - 1; ++l) { c /= 2; D.c[l] = c; D.off[l] = off; off += c; }
+    D.c_last = c; D.off_last = off;
+    D.base.C = cf->residual_channels; D.base.Cd = cf->dilation_channels; D.base.Cs = cf->skip_channels; D.base.depth = cf->depth;
+    D.base.radix = cf->radix; D.base.prec = cf->precision; D.base.bias = cf->bias ? 1 : 0; D.base.ic = 1; D.base.aux = 1;
+    return D;
+}
+static int mr_model_check(const wg_mr_config *cf)
+{
+    int rc = mr_cfg_check(cf);
+    if (rc) return rc;
+    const MrDims D = mr_dims(cf);
+    if (D.pf && (rc = wn_check(D.prior_wn()))) return rc;
+    for (int l = 0; l < D.L - 1 && D.fl; ++l)
+        if ((rc = wn_check(D.level_wn(l)))) return rc;
+    return WG_OK;
+}
+
+struct MrPack {
+    size_t ones, lu, wn[WG_MAX_FLOWS], total;
+};
+static MrPack mr_pack_layout(const MrDims &D)
+{
+    MrPack L;
+    Bump bp;
+    L.ones = bp.take(WG_ONES);
+    L.lu = bp.take((size_t)D.nflows * WG_LU_STRIDE);
+    for (int k = 0; k < D.nflows; ++k) L.wn[k] = bp.take(wn_pack_layout(D.flow_wn(k)).total);
+    L.total = bp.off;
+    return L;
+}
+// Table entries of flow k in the state dict's order: its 1x1 weight, and the first entry of its WN
+static int mr_table_w(const MrDims &D, int k) { return k < D.pf ? k : D.pf + D.pf * D.base.nparams() + (k - D.pf); }
+static int mr_table_wn(const MrDims &D, int k)
+{
+    const int nW = D.base.nparams();
+    return k < D.pf ? D.pf + k * nW : D.pf + D.pf * nW + (D.L - 1) * D.fl + (k - D.pf) * nW;
+}
+// the WN's entries in WnD's order (V, start, (W_i, W_o_i) x depth as (g, v) pairs, end, then the biases) from the state dict's, where a
+// conv with a bias lists it in front of its (g, v) pair and `end` behind its weight
+static void mr_wn_table(const WnD &d, const float *const *src, const float **dst)
+{
+    const int nconv = 2 + 2 * d.depth;
+    if (!d.bias) { for (int i = 0; i < d.nparams(); ++i) dst[i] = src[i]; return; }
+    for (int j = 0; j < nconv; ++j) { dst[d.pb(j)] = src[3 * j]; dst[2 * j] = src[3 * j + 1]; dst[2 * j + 1] = src[3 * j + 2]; }
+    dst[2 * nconv] = src[3 * nconv];
+    dst[d.pb(nconv)] = src[3 * nconv + 1];
+}
+
+struct MrWs {
+    Geo g;
+    int Gp, ntile, melp, condp[MR_MAX_LEVELS];
+    size_t X, partial, mel, melS, cond[MR_MAX_LEVELS], condS[MR_MAX_LEVELS], total;
+    WnWs wnp, wn[MR_MAX_LEVELS];                             // the prior's WN planes, each level's (WNs of different (in, aux) never share planes:
+};                                                          // their layouts differ, and a halo column must never have held another WN's data)
+static MrWs mr_ws_layout(const MrDims &D, int B, int T)
+{
+    MrWs w = {};
+    w.g = make_geo(B, T, D.base.maxdil() * (D.base.radix - 1) / 2);
+    w.Gp = rup(D.G, WG_BK) + WG_BK;
+    w.ntile = w.g.Tt / WG_AFF_T;
+    const int prec = D.base.prec;
+    Bump bp;
+    w.X = bp.take((size_t)B * w.Gp * w.g.P);
+    w.partial = bp.take((size_t)D.nflows * B * w.ntile);
+    if (D.pf) {
+        const WnD d = D.prior_wn();
+        w.melp = d.auxp();
+        w.mel = bp.take((size_t)B * w.melp * w.g.P);
+        if (prec == 2) w.melS = bp.take((size_t)B * w.melp * w.g.P);
+        wn_ws_layout(bp, d, d.ic, w.g, 0, prec, w.wnp);
+    }
+    for (int l = 0; l < D.L - 1; ++l) {
+        const WnD d = D.level_wn(l);
+        w.condp[l] = d.auxp();
+        w.cond[l] = bp.take((size_t)B * w.condp[l] * w.g.P);
+        if (!D.fl) continue;                                 // (no level flows: the plane only carries the average to the next stage)
+        if (prec == 2) w.condS[l] = bp.take((size_t)B * w.condp[l] * w.g.P);
+        wn_ws_layout(bp, d, d.ic, w.g, 0, prec, w.wn[l]);
+    }
+    w.total = bp.off + 4096;
+    return w;
+}
+
+// ---- the plane kernels' launch helpers (wg_mr_planes.h) ----
+static bool mr_aligned(const PRef &r) { return !r.p || mr::aligned16(r.p); }
+static void mr_run_split(Ctx &cx, const Geo &g, const float *audio, int N, PRef src, PRef diff, PRef cond, PRef avg, int half)
+{
+    mr::PlaneSplitArgs p;
+    p.audio = audio; p.src = src; p.diff = diff; p.cond = cond; p.avg = avg; p.g = g; p.half = half; p.N = N;
+    p.vec = audio ? (half % 2 == 0 && mr::aligned16(audio)) : (mr_aligned(src) && mr_aligned(diff) && mr_aligned(cond) && mr_aligned(avg));
+    const unsigned nb = mr::blocks_for(audio ? (long long)g.B * g.T : (long long)g.B * half * ((g.T + 3) / 4));
+    if (!nb) { if (!cx.err) cx.err = WG_EUNSUPPORTED; return; }
+    WG_LAUNCH(cx, mr::plane_split_kernel, dim3(nb), dim3(256), 0, p);
+}
+static void mr_run_merge(Ctx &cx, const Geo &g, PRef avg, PRef diff, PRef out, float *audio, int N, int half)
+{
+    mr::PlaneMergeArgs p;
+    p.avg = avg; p.diff = diff; p.out = out; p.audio = audio; p.g = g; p.half = half; p.N = N;
+    p.vec = out.p ? (mr_aligned(avg) && mr_aligned(diff) && mr_aligned(out)) : (half % 2 == 0 && mr::aligned16(audio));
+    const unsigned nb = mr::blocks_for(out.p ? (long long)g.B * half * ((g.T + 3) / 4) : (long long)g.B * g.T);
+    if (!nb) { if (!cx.err) cx.err = WG_EUNSUPPORTED; return; }
+    WG_LAUNCH(cx, mr::plane_merge_kernel, dim3(nb), dim3(256), 0, p);
+}
+static void mr_run_upsample(Ctx &cx, const Geo &g, const float *h, int n_mels, int F, int s, const PRef *dst, int nd)
+{
+    mr::PlaneUpArgs p;
+    memset(&p, 0, sizeof(p));
+    p.h = h; p.g = g; p.nd = nd; p.n_mels = n_mels; p.F = F; p.s = s; p.vec = 1;
+    for (int j = 0; j < nd; ++j) { p.dst[j] = dst[j]; p.vec = p.vec && mr_aligned(dst[j]); }
+    const unsigned nb = mr::blocks_for((long long)g.B * n_mels * ((g.T + 3) / 4));
+    if (!nb) { if (!cx.err) cx.err = WG_EUNSUPPORTED; return; }
+    WG_LAUNCH(cx, mr::plane_upsample_kernel, dim3(nb), dim3(256), 0, p);
+}
+static void mr_run_copy(Ctx &cx, const Geo &g, PRef src, PRef dst, int rows)
+{
+    const unsigned nb = mr::blocks_for((long long)g.B * rows * ((g.T + 3) / 4));
+    if (!nb) { if (!cx.err) cx.err = WG_EUNSUPPORTED; return; }
+    WG_LAUNCH(cx, mr::plane_copy_kernel, dim3(nb), dim3(256), 0, src, dst, g, rows, (int)(mr_aligned(src) && mr_aligned(dst)));
+}
+
+int wg_mr_check(const wg_mr_config *cf, int B, int N, int F)
+{
+    const int rc = mr_model_check(cf);
+    if (rc) return rc;
+    if (B < 1 || N < 1 || F < 1) return WG_EINVAL;
+    if (N % cf->n_group) return WG_ESHAPE;
+    const int T = N / cf->n_group, s = cf->hop_size / cf->n_group;
+    if ((long long)F * s > 0x3fffffffLL) return WG_EUNSUPPORTED;         // 2t + 1 - s stays an int (up_source)
+    if (T > (long long)F * s) return WG_ESHAPE;                          // assert x.size(2) <= y.size(2)  (mr_waveglow.py:65, :99)
+    if (B > 65535 || (long long)B * N > 0x7fffffffLL) return WG_EUNSUPPORTED;      // items are a grid axis; one thread per (item, column)
+    return WG_OK;
+}
+int wg_mr_param_count(const wg_mr_config *cf)
+{
+    if (mr_model_check(cf)) return 0;
+    const MrDims D = mr_dims(cf);
+    return D.nflows * (1 + D.base.nparams());
+}
+size_t wg_mr_packed_bytes(const wg_mr_config *cf) { return mr_model_check(cf) ? 0 : mr_pack_layout(mr_dims(cf)).total * sizeof(float); }
+size_t wg_mr_workspace_bytes(const wg_mr_config *cf, int B, int N)
+{
+    if (mr_model_check(cf) || B < 1 || N < 1 || N % cf->n_group) return 0;
+    const int s = cf->hop_size / cf->n_group, T = N / cf->n_group;
+    if (wg_mr_check(cf, B, N, (T + s - 1) / s)) return 0;
+    return mr_ws_layout(mr_dims(cf), B, T).total * sizeof(float);
+}
+long long wg_stat_mr_pass_calls(void) { return g_mr_pass_calls.load(std::memory_order_relaxed); }
+
+int wg_mr_pack_weights(const wg_mr_config *cf, const void *const *table, void *packed, void *stream)
+{
+    int rc = mr_model_check(cf);
+    if (rc) return rc;
+    if (!table || !packed) return WG_EINVAL;
+    const MrDims D = mr_dims(cf);
+    const int nW = D.base.nparams(), nconv = 2 + 2 * D.base.depth;
+    const float *const *t = (const float *const *)table;
+    std::vector<const float *> tab((size_t)D.nflows * nW);
+    for (int k = 0; k < D.nflows; ++k) {
+        const WnD d = D.flow_wn(k);
+        if (!t[mr_table_w(D, k)]) return WG_EINVAL;
+        mr_wn_table(d, t + mr_table_wn(D, k), tab.data() + (size_t)k * nW);
+        for (int i = 0; i < nW; ++i)                                     // only a weight_g may be absent (a conv whose weight norm was removed)
+            if (!tab[(size_t)k * nW + i] && !(i < 2 * nconv && !(i & 1))) return WG_EINVAL;
+    }
+    Ctx cx = {(hipStream_t)stream, 0, 0};
+    float *pk = (float *)packed;
+    const MrPack M = mr_pack_layout(D);
+    float *ones = pk + M.ones;
+    WG_LAUNCH(cx, fill_rows_kernel, dim3(WG_ONES / 256, 1, 1), dim3(256), 0, pref(ones, 1), Geo{1, WG_ONES, WG_ONES, 0, WG_ONES}, (const float *)nullptr, 1.0f);
+    LuArgs lu;                                                           // per 1x1: W, W^-1, log|det W| (what wg_invconv_apply forms per call)
+    lu.n = D.nflows; lu.out = pk + M.lu; lu.ostride = WG_LU_STRIDE;
+    for (int k = 0; k < D.nflows; ++k) { lu.job[k].W = t[mr_table_w(D, k)]; lu.job[k].c = D.flow_c(k); }
+    WG_LAUNCH(cx, lu_kernel, dim3((D.nflows + 63) / 64), dim3(64), 0, lu);
+    auto P = [&](int k) { return tab.data() + (size_t)k * nW; };
+    JobBatch jb(&cx);
+    for (int k = 0; k < D.nflows; ++k) { const WnD d = D.flow_wn(k); wn_pack_norms(jb, d, wn_pack_layout(d), P(k), pk + M.wn[k]); }
+    jb.flush_norm();
+    EffBatch eb(&cx);
+    for (int k = 0; k < D.nflows; ++k) { const WnD d = D.flow_wn(k); wn_pack_eff(eb, d, wn_pack_layout(d), P(k), pk + M.wn[k]); }
+    eb.flush();
+    FoldBatch fb(&cx);
+    for (int k = 0; k < D.nflows; ++k) { const WnD d = D.flow_wn(k); wn_pack_fold(fb, d, wn_pack_layout(d), P(k), pk + M.wn[k]); }
+    fb.flush();
+    for (int k = 0; k < D.nflows; ++k) { const WnD d = D.flow_wn(k); wn_pack_mats(jb, d, wn_pack_layout(d), P(k), pk + M.wn[k], ones); }
+    jb.flush_pack();
+    ImgBatch ib(&cx);
+    for (int k = 0; k < D.nflows; ++k) { const WnD d = D.flow_wn(k); wn_pack_images(ib, d, wn_pack_layout(d), pk + M.wn[k]); }
+    ib.flush();
+    return cx.err;
+}
+
+// dir 0: forward_computation (audio -> latent), 1: reverse_computation.  The blocks' arithmetic: the couplings and the prior 1x1 convs
+// take the model's reverse_mode, the level 1x1 convs never do (mr_waveglow.py:14-17), so the sign of T log|det W| is per flow.
+static int mr_pass(const wg_mr_config *cf, const void *packed, const float *in, const float *h, int B, int N, int F, int dir, float *out,
+                   float *logdet, void *wsv, size_t ws_bytes, void *stream)
+{
+    if (!cf || !packed || !in || !h || !out || !logdet || !wsv) return WG_EINVAL;
+    const int rc = wg_mr_check(cf, B, N, F);
+    if (rc) return rc;
+    const MrDims D = mr_dims(cf);
+    const int T = N / D.G;
+    const MrWs W = mr_ws_layout(D, B, T);
+    if (W.total * sizeof(float) > ws_bytes) return WG_EWORKSPACE;
+    const MrPack M = mr_pack_layout(D);
+    Ctx cx = {(hipStream_t)stream, 0, cf->precision};
+    const float *pk = (const float *)packed;
+    float *ws = (float *)wsv;
+    const Geo g = W.g;
+    const bool sp = cx.prec == 2;
+    const int aff = (dir != 0) != (D.rm != 0) ? AFF_REV : AFF_FWD;
+    const bool prior_inv = aff == AFF_REV, level_inv = dir != 0;
+    float *partial = ws + W.partial;
+    const PRef X = pref(ws + W.X, W.Gp);
+    const dim3 cgrid((T + 255) / 256, B);
+    auto cond = [&](int l) { return pref(ws + W.cond[l], W.condp[l]); };
+    if (D.pf) layer_sync_clear(cx, ws, W.wnp.lsync);
+    for (int l = 0; l < D.L - 1 && D.fl; ++l) layer_sync_clear(cx, ws, W.wn[l].lsync);
+
+    WnRun r;
+    r.g = g; r.ws = ws; r.save = 0;
+    auto coupling = [&](int k, const WnD &d, const WnWs &w, int base, const float *Y, const float *YS) {
+        r.d = d; r.L = wn_pack_layout(d); r.pk = pk + M.wn[k]; r.w = w; r.X = pref(ws + W.X, W.Gp, base); r.Y = Y; r.YS = YS;
+        wn_forward(cx, r);
+        run_end_affine(cx, r, aff, pnull(), nullptr, nullptr, nullptr, partial + (size_t)k * B * W.ntile);
+    };
+    auto mix = [&](int k, int base, int c, bool inv) {
+        run_mix(cx, g, pref(ws + W.X, W.Gp, base), c, pk + M.lu + (size_t)k * WG_LU_STRIDE + (inv ? WG_MAXC * WG_MAXC : 0), 0);
+    };
+    auto prior_flow = [&](int k) {
+        const WnD d = D.prior_wn();
+        if (!dir) mix(k, D.off_last, D.c_last, prior_inv);
+        coupling(k, d, W.wnp, D.off_last, ws + W.mel, ws + W.melS);
+        if (dir) mix(k, D.off_last, D.c_last, prior_inv);
+    };
+    auto level_flow = [&](int l, int j) {
+        const WnD d = D.level_wn(l);
+        const int k = D.pf + l * D.fl + j;
+        if (!dir) mix(k, D.off[l], D.c[l], level_inv);
+        coupling(k, d, W.wn[l], D.off[l], ws + W.cond[l], ws + W.condS[l]);
+        if (dir) mix(k, D.off[l], D.c[l], level_inv);
+    };
+    auto level_splane = [&](int l) { if (sp && D.fl) run_to_splane(cx, g, cond(l), D.level_wn(l).aux, ws + W.condS[l], W.condp[l]); };
+
+    // the mel, read once: into the prior's plane and behind the average of every level's plane
+    PRef up[MR_MAX_DST];
+    int nd = 0;
+    if (D.pf) up[nd++] = pref(ws + W.mel, W.melp);
+    for (int l = 0; l < D.L - 1 && D.fl && !D.sr; ++l) up[nd++] = pref(ws + W.cond[l], W.condp[l], D.c[l]);
+    if (nd) mr_run_upsample(cx, g, h, D.mels, F, D.s, up, nd);
+    if (D.pf && sp) run_to_splane(cx, g, pref(ws + W.mel, W.melp), D.mels, ws + W.melS, W.melp);
+
+    if (!dir) {                                               // mr_waveglow.py forward_computation
+        if (D.L == 1) WG_LAUNCH(cx, squeeze_kernel, cgrid, dim3(256), 0, in, X, g, D.G, N);
+        for (int l = 0; l < D.L - 1; ++l) {
+            // level 0 reads the audio itself, level l the average in level l - 1's conditioning plane; the last level's average is
+            // also the state the prior flows work on
+            mr_run_split(cx, g, l ? nullptr : in, N, l ? cond(l - 1) : pnull(), pref(ws + W.X, W.Gp, D.off[l]), cond(l),
+                         l == D.L - 2 ? pref(ws + W.X, W.Gp, D.off_last) : pnull(), D.c[l]);
+            level_splane(l);
+            for (int j = 0; j < D.fl; ++j) level_flow(l, j);
+        }
+        for (int k = 0; k < D.pf; ++k) prior_flow(k);
+        WG_LAUNCH(cx, unsqueeze_kernel, cgrid, dim3(256), 0, X, out, g, D.G, N);
+    } else {                                                  // reverse_computation
+        WG_LAUNCH(cx, squeeze_kernel, cgrid, dim3(256), 0, in, X, g, D.G, N);
+        for (int k = D.pf - 1; k >= 0; --k) prior_flow(k);
+        if (D.L == 1) WG_LAUNCH(cx, unsqueeze_kernel, cgrid, dim3(256), 0, X, out, g, D.G, N);
+        else mr_run_copy(cx, g, pref(ws + W.X, W.Gp, D.off_last), cond(D.L - 2), D.c_last);
+        for (int l = D.L - 2; l >= 0; --l) {
+            level_splane(l);                                  // (the whole plane once, when its average has arrived)
+            for (int j = D.fl - 1; j >= 0; --j) level_flow(l, j);
+            // the merged channels are level l - 1's average: straight into its conditioning plane, or (the last merge) the audio
+            mr_run_merge(cx, g, cond(l), pref(ws + W.X, W.Gp, D.off[l]), l ? cond(l - 1) : pnull(), l ? nullptr : out, N, D.c[l]);
+        }
+    }
+    WG_LAUNCH(cx, mr::logdet_finalize2_kernel, dim3(B), dim3(64), 0, pk + M.lu, WG_LU_STRIDE, D.nflows, D.pf, prior_inv ? -(float)T : (float)T,
+              level_inv ? -(float)T : (float)T, (const float *)partial, W.ntile, B, logdet);
+    if (!cx.err) g_mr_pass_calls.fetch_add(1, std::memory_order_relaxed);
+    return cx.err;
+}
+int wg_mr_forward(const wg_mr_config *cf, const void *packed, const float *audio, const float *h, int B, int N, int F,
+                  float *z, float *logdet, void *ws, size_t ws_bytes, void *stream)
+{
+    return mr_pass(cf, packed, audio, h, B, N, F, 0, z, logdet, ws, ws_bytes, stream);
+}
+int wg_mr_inverse(const wg_mr_config *cf, const void *packed, const float *z, const float *h, int B, int N, int F,
+                  float *x, float *logdet, void *ws, size_t ws_bytes, void *stream)
+{
+    return mr_pass(cf, packed, z, h, B, N, F, 1, x, logdet, ws, ws_bytes, stream);
+}
+
+// The plane kernels on their own, through the passes' launch helpers (what the tests measure them through).  A plane is
+// [B][rows][P] floats with P = H + roundup(T, 128) + H and column t at H + t (wg_mr_plane_geo); a kernel writes columns [0, T) of the rows it
+// owns and nothing else.
+int wg_mr_plane_geo(int T, int halo, int *H, int *P)
+{
+    if (T < 1 || halo < 0 || !H || !P) return WG_EINVAL;
+    const Geo g = make_geo(1, T, halo);
+    *H = g.H; *P = g.P;
+    return WG_OK;
+}
+static bool mr_plane_ok(const void *p, int rows, int ch0, int n) { return p && rows >= 1 && ch0 >= 0 && n >= 1 && (long long)ch0 + n <= rows; }
+int wg_mr_plane_split(const float *audio, const float *src, int src_rows, int B, int T, int halo, int c, float *diff, int diff_rows, int diff_ch0,
+                      float *cond, int cond_rows, float *avg, int avg_rows, int avg_ch0, void *stream)
+{
+    if (B < 1 || T < 1 || halo < 0 || c < 2 || (c & 1) || (!audio == !src)) return WG_EINVAL;
+    if ((src && !mr_plane_ok(src, src_rows, 0, c)) || !mr_plane_ok(diff, diff_rows, diff_ch0, c / 2) || !mr_plane_ok(cond, cond_rows, 0, c / 2) ||
+        (avg && !mr_plane_ok(avg, avg_rows, avg_ch0, c / 2)))
+        return WG_EINVAL;
+    Ctx cx = {(hipStream_t)stream, 0, 0};
+    mr_run_split(cx, make_geo(B, T, halo), audio, T * c, src ? pref((float *)src, src_rows) : pnull(), pref(diff, diff_rows, diff_ch0),
+                 pref(cond, cond_rows), avg ? pref(avg, avg_rows, avg_ch0) : pnull(), c / 2);
+    return cx.err;
+}
+int wg_mr_plane_merge(const float *avg, int avg_rows, const float *diff, int diff_rows, int diff_ch0, int B, int T, int halo, int c, float *out,
+                      int out_rows, float *audio, void *stream)
+{
+    if (B < 1 || T < 1 || halo < 0 || c < 2 || (c & 1) || (!audio == !out)) return WG_EINVAL;
+    if (!mr_plane_ok(avg, avg_rows, 0, c / 2) || !mr_plane_ok(diff, diff_rows, diff_ch0, c / 2) || (out && !mr_plane_ok(out, out_rows, 0, c)))
+        return WG_EINVAL;
+    Ctx cx = {(hipStream_t)stream, 0, 0};
+    mr_run_merge(cx, make_geo(B, T, halo), pref((float *)avg, avg_rows), pref((float *)diff, diff_rows, diff_ch0),
+                 out ? pref(out, out_rows) : pnull(), audio, T * c, c / 2);
+    return cx.err;
+}
+int wg_mr_plane_upsample(const float *h, int B, int n_mels, int F, int s, int T, int halo, int nd, float *const *planes, const int *rows,
+                         const int *ch0, void *stream)
+{
+    if (!h || B < 1 || n_mels < 1 || F < 1 || s < 1 || T < 1 || halo < 0 || nd < 1 || nd > MR_MAX_DST || !planes || !rows || !ch0) return WG_EINVAL;
+    if ((long long)F * s > 0x3fffffffLL) return WG_EUNSUPPORTED;
+    if (T > (long long)F * s) return WG_ESHAPE;
+    PRef dst[MR_MAX_DST];
+    for (int j = 0; j < nd; ++j) {
+        if (!mr_plane_ok(planes[j], rows[j], ch0[j], n_mels)) return WG_EINVAL;
+        dst[j] = pref(planes[j], rows[j], ch0[j]);
+    }
+    Ctx cx = {(hipStream_t)stream, 0, 0};
+    mr_run_upsample(cx, make_geo(B, T, halo), h, n_mels, F, s, dst, nd);
+    return cx.err;
 }
 
 

@@ -127,11 +127,16 @@ class PackedWeights:
         self.key = None
         self._pending = None
 
-    def stale(self, params):
+    @staticmethod
+    def key_of(params):
+        return tuple((p.data_ptr(), p._version) if p is not None else None for p in params)
+
+    def stale(self, params, key=None):
         """True: `params` differ from what `buf` holds.  The buffer then counts as EMPTY until commit(): a pack that raises half way
         (a CPU or half parameter further down the table, an unsupported configuration, a failed launch) must not leave a key behind
-        under which a retry would run on the old or half-written weights."""
-        key = tuple((p.data_ptr(), p._version) if p is not None else None for p in params)
+        under which a retry would run on the old or half-written weights.  `key`: key_of(params), where the caller has it already."""
+        if key is None:
+            key = self.key_of(params)
         if key != self.key or self.buf is None:
             self.key, self._pending = None, key
             return True
@@ -143,7 +148,8 @@ class PackedWeights:
 
 
 class _InverseGraphs:
-    """The WG_GRAPHS / auto-capture policy of a model's synthesis call, shared by the engines that have one (ModelEngine, MelGlowEngine).
+    """The WG_GRAPHS / auto-capture policy of a model's synthesis call, shared by the engines that have one (ModelEngine, MelGlowEngine,
+    MRWaveGlowEngine).
     `launch(z, h) -> (out, logdet)` enqueues the whole call on the current stream and allocates its two outputs."""
 
     def __init__(self):
@@ -1066,3 +1072,63 @@ def mr_unpack(src, n_group, off, c):
     dst = _f32((Bn, c, T), src)
     check(_lib.lib().wg_mr_unpack(_p(src), Bn, c, T, n_group, off, _p(dst), _stream(src.device)), "wg_mr_unpack")
     return dst
+
+
+# ---- MRWaveGlow's eval passes (include/wgflow.h wg_mr_check .. wg_mr_inverse) ----------------------------------------------------------
+class MRWaveGlowEngine(_InverseGraphs):
+    """Model-level, no-autograd passes of MRWaveGlow: wg_mr_pack_weights once per weight change, then wg_mr_forward / wg_mr_inverse
+    from the packed weights and one zero-initialised workspace.  `params`: the model's state-dict tensors in the header's order."""
+
+    def __init__(self, cfg):
+        super().__init__()
+        self.cfg = cfg
+        self.buffers = _Buffers()
+        self.packed = PackedWeights()
+        self.n_params = None
+
+    def check(self, B, N, F):
+        """0, or the library's error code for a call the passes do not serve (no launch, no device needed)."""
+        return _lib.lib().wg_mr_check(C.byref(self.cfg), B, N, F)
+
+    def _pack(self, params, device, key=None):
+        L = _lib.lib()
+        if self.n_params is None:
+            self.n_params = L.wg_mr_param_count(C.byref(self.cfg))
+        if len(params) != self.n_params:
+            raise WgError("MRWaveGlow parameter table has %d entries, expected %d" % (len(params), self.n_params))
+        if self.packed.stale(params, key) or self.packed.buf.device != device:
+            require_device(*params)
+            nbytes = L.wg_mr_packed_bytes(C.byref(self.cfg))
+            if nbytes == 0:
+                raise WgError("MRWaveGlow configuration not supported by the one-call passes (include/wgflow.h wg_mr_check)")
+            if self.packed.buf is None or self.packed.buf.numel() < nbytes or self.packed.buf.device != device:
+                self.packed.buf = torch.empty(nbytes, dtype=torch.uint8, device=device)
+            check(L.wg_mr_pack_weights(C.byref(self.cfg), _table([t.contiguous() if t is not None else None for t in params]),
+                                       _p(self.packed.buf), _stream()), "wg_mr_pack_weights")
+            self.packed.commit()
+        return self.packed.buf
+
+    def _launch(self, pk, ws, x, h, inverse):
+        B, N = x.shape
+        out = torch.empty_like(x)
+        logdet = torch.empty(B, dtype=torch.float32, device=x.device)
+        fn = _lib.lib().wg_mr_inverse if inverse else _lib.lib().wg_mr_forward
+        check(fn(C.byref(self.cfg), _p(pk), _p(x), _p(h), B, N, h.shape[2], _p(out), _p(logdet), _p(ws), ws.numel(), _stream()),
+              "wg_mr_inverse" if inverse else "wg_mr_forward")
+        return out, logdet
+
+    @on_device
+    def run(self, params, x, h, inverse, key=None):
+        """x [B, N], h [B, n_mels, F]; inverse: reverse_computation.  The pass towards the audio (reverse_computation, or
+        forward_computation of a reverse_mode model) may be replayed from a captured graph (WG_GRAPHS, keyed as ModelEngine.run).
+        `key`: PackedWeights.key_of(params), where the caller has it already."""
+        require_device(x, h)
+        x, h = x.contiguous(), h.contiguous()
+        B, N = x.shape
+        pk = self._pack(params, x.device, key)
+        nbytes = _lib.lib().wg_mr_workspace_bytes(C.byref(self.cfg), B, N)
+        ws = self.buffers.get((x.device, B, N), nbytes, x.device)
+        if bool(inverse) != bool(self.cfg.reverse_mode):
+            key = (x.device, tuple(x.shape), h.shape[2], pk.data_ptr(), ws.data_ptr(), bool(inverse))
+            return self._run_inverse(key, lambda sz, sh: self._launch(pk, ws, sz, sh, inverse), x, h)
+        return self._launch(pk, ws, x, h, inverse)

@@ -19,11 +19,18 @@ Upstream's quirks are kept, because checkpoints and results depend on them:
 A memory-efficient block frees the storage of the tensor it is handed.  No block here is ever handed a view of a conditioning buffer or
 of the caller's tensors: the split writes the average twice (its own tensor, which the next stage may free, and the rows of the
 conditioning buffer, which the couplings keep), level 0 reads the audio through its strides, and the latents are packed by a kernel.
+In eval() with autograd disabled a whole pass is ONE library call instead (MRWaveGlow._engine_pass: wg_mr_forward / wg_mr_inverse from
+weights packed once per weight change, the state in the engine's planes from the first kernel to the last, the pass towards the audio
+replayed from a captured graph under the WG_GRAPHS policy); everything else -- train(), autograd enabled, WG_MR_ENGINE=0, a
+configuration wg_mr_check refuses -- is the module path below, unchanged.
+
 With super_resolution upstream hands the very same tensor to the last level's couplings as conditioning and to the first prior 1x1
 conv, which frees it and rebuilds it in its backward; here the two are separate tensors with the same values.  Upstream's level
 couplings therefore run their backward on a conditioning tensor rebuilt to about 1e-7, these on the original: with super_resolution
 the gradients differ from upstream's in the last bits (far inside the 1e-4 bars the fixtures are held to).
 """
+import os
+import weakref
 from typing import Tuple
 
 import torch
@@ -31,10 +38,13 @@ from torch import Tensor, nn
 from torch.autograd import Function
 
 from . import engine
-from ._lib import WgError
+from ._lib import WgError, WgMrConfig, default_precision
 from .base import FlowBase
 from .efficient_modules import AffineCouplingBlock, InvertibleConv1x1
+from .utils import SlotTable, conv_gv_slots
 from .waveglow import WN
+
+_ENGINES = weakref.WeakKeyDictionary()      # model -> engine.MRWaveGlowEngine (packed weights, workspaces, graphs): not part of the module's state
 
 __all__ = ["MRWaveGlow"]
 
@@ -184,6 +194,86 @@ class MRWaveGlow(FlowBase):
             self.prior_invconv1x1.append(InvertibleConv1x1(c, memory_efficient=memory_efficient, reverse_mode=reverse_mode))
             self.prior_WNs.append(AffineCouplingBlock(WN, memory_efficient=memory_efficient, in_channels=c // 2, aux_channels=n_mels,
                                                       reverse_mode=reverse_mode, **kwargs))
+        self._mr_table = SlotTable("mr_slots")
+
+    # ---- the one-call engine (wg_mr_forward / wg_mr_inverse) ------------------------------------------------------------------------
+    def mr_slots(self):
+        """Where every entry of the C ABI's table lives in the module tree: state_dict() order, a conv's (weight_g, weight_v) pair as
+        (None, weight) once weight norm was removed."""
+        def wn_slots(wn):
+            convs = [wn.V, wn.start] + [c for layer in wn.layers for c in (layer.W, layer.W_o)]
+            out = []
+            for conv in convs:
+                out += ([(conv._parameters, "bias")] if wn.has_bias else []) + list(conv_gv_slots(conv))
+            return out + [(wn.end._parameters, "weight")] + ([(wn.end._parameters, "bias")] if wn.has_bias else [])
+
+        slots = [(m._parameters, "weight") for m in self.prior_invconv1x1]
+        for blk in self.prior_WNs:
+            slots += wn_slots(blk.F)
+        slots += [(m._parameters, "weight") for level in self.invconv1x1_list for m in level]
+        for level in self.WNs_list:
+            for blk in level:
+                slots += wn_slots(blk.F)
+        return slots
+
+    def mr_table(self):
+        return self._mr_table(self)
+
+    def mr_config(self, precision=None):
+        wn = next((b.F for b in list(self.prior_WNs) + [b for level in self.WNs_list for b in level]), None)
+        sizes = (0,) * 6 if wn is None else (wn.dil_chs, wn.res_chs, wn.skp_chs, len(wn.layers), wn.rdx, int(wn.has_bias))
+        return WgMrConfig(self.prior_flows, self.flows, self.levels, self.n_group, self._hop_length, self.n_mels, int(self.super_resolution),
+                          int(self._reverse_mode), *sizes, default_precision() if precision is None else precision)
+
+    def mr_engine(self):
+        """the engine of the arithmetic WG_PRECISION names right now (read per call, as the blocks read it when they are built)"""
+        per_model = _ENGINES.get(self)
+        if per_model is None:
+            per_model = _ENGINES[self] = {}
+        prec = default_precision()
+        eng = per_model.get(prec)
+        if eng is None:
+            eng = per_model[prec] = engine.MRWaveGlowEngine(self.mr_config(prec))
+        return eng
+
+    def _engine_route(self, x, h):
+        """(None, table, key) when this call goes through the one-call engine, else (why not, None, None): the module path runs.  The
+        engine serves exactly: autograd disabled, the model in eval(), CUDA float32 contiguous tensors, a call wg_mr_check accepts, and
+        WG_MR_ENGINE (read per call) not "0".  A synthesis call pays for this on the host before its first launch, so nothing here walks
+        the module tree: the table and the module list come from the cached slots, and the parameters' dtype and device are looked at
+        only when they are not the ones the engine has packed (`key`, what PackedWeights tracks: address and version of each)."""
+        if os.environ.get("WG_MR_ENGINE") == "0":
+            return "WG_MR_ENGINE=0", None, None
+        if torch.is_grad_enabled():
+            return "autograd is enabled", None, None
+        table = self.mr_table()
+        for m in self._mr_table.modules():
+            if m.training:
+                return "a module is in train()", None, None
+        if x.dim() != 2 or h.dim() != 3 or x.size(0) != h.size(0) or h.size(1) != self.n_mels:
+            return "not audio [B, N] with conditioning [B, n_mels, frames]", None, None
+        eng = self.mr_engine()
+        key = eng.packed.key_of(table)
+        packed = key == eng.packed.key and eng.packed.buf is not None       # these very tensors were packed: float32, on buf's device
+        if not packed and any(t is not None and t.dtype != torch.float32 for t in table):
+            return "parameters are not float32", None, None
+        rc = eng.check(x.size(0), x.size(1), h.size(2))
+        if rc:
+            return "wg_mr_check: code %d" % rc, None, None
+        if not (x.is_cuda and x.dtype == torch.float32 and h.dtype == torch.float32 and h.device == x.device and
+                (eng.packed.buf.device == x.device if packed else all(t is None or t.device == x.device for t in table))):
+            return "tensors are not float32 on one HIP device", None, None
+        if not (x.is_contiguous() and h.is_contiguous()):
+            return "tensors are not contiguous", None, None
+        return None, table, key
+
+    def _engine_pass(self, x, h, inverse):
+        """forward_computation / reverse_computation as one library call (wg_mr_forward / wg_mr_inverse), or None: the module path runs.
+        The caller's tensors are only read."""
+        why, table, key = self._engine_route(x, h)
+        if why is not None:
+            return None
+        return self.mr_engine().run(table, x, h, inverse, key)        # (autograd is disabled: the parameters need no detach())
 
     def _check(self, x: Tensor, h: Tensor) -> int:
         """The number of columns T of x [B, N] as [B, n_group, T]; WgError for what the kernels would refuse, before any launch."""
@@ -199,6 +289,9 @@ class MRWaveGlow(FlowBase):
         return T
 
     def forward_computation(self, x: Tensor, h: Tensor) -> Tuple[Tensor, Tensor]:
+        out = self._engine_pass(x, h, False)
+        if out is not None:
+            return out
         T = self._check(x, h)
         B, s = x.size(0), self.upsample_factor
         if self.levels == 1:
@@ -224,6 +317,9 @@ class MRWaveGlow(FlowBase):
         return _Pack.apply(self.n_group, *emitted), logdet
 
     def reverse_computation(self, z: Tensor, h: Tensor) -> Tuple[Tensor, Tensor]:
+        out = self._engine_pass(z, h, True)
+        if out is not None:
+            return out
         T = self._check(z, h)
         s = self.upsample_factor
         *remained, z = _Unpack.apply(z, self.n_group, tuple(self.z_split_sizes))

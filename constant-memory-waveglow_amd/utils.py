@@ -68,9 +68,15 @@ class SlotTable:
         import weakref
         slots = getattr(owner, self._method)()
         edges = [(m._modules, name, child) for m in owner.modules() for name, child in m._modules.items()]
-        state = (weakref.ref(owner), slots, edges)
+        state = (weakref.ref(owner), slots, edges, [owner] + [c for _, _, c in edges if c is not None])
         self._state = state
         return state
+
+    def modules(self):
+        """Every module of the tree the last call resolved or re-checked, as a flat list (the owner and the child of every edge): what
+        owner.modules() walks, without the walk."""
+        state = self._state
+        return [] if state is None else state[3]
 
     @staticmethod
     def _valid(state, owner):

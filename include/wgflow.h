@@ -526,6 +526,78 @@ int    wg_mg_layer_apply(const wg_lvc_dims *d, int skip_ch, int first, int last,
 int    wg_mg_predictor_apply(const wg_mg_config *cfg, const void *packed, int flow, const float *h, int B, int Fr, int F, float *kernels,
                              void *ws, size_t ws_bytes, void *stream);
 
+/* ---- MRWaveGlow, model level: the eval-mode passes (model/mr_waveglow.py:56-136 upstream) ---------------------------------------
+ * Appended to revision 10 without changing any earlier declaration (purely additive: the revision stays 10).  What wg_forward /
+ * wg_inverse are to WaveGlow: MRWaveGlow.forward_computation / reverse_computation as ONE call each, from weights packed once per
+ * weight change and one zero-initialised workspace (wg_workspace_init once; the passes keep every halo and padding row zero).  The WNs
+ * and the 1x1 mixes are the kernels wg_forward runs, in the arithmetic `precision` names (WG_PREC_*); the Haar splits and merges and
+ * the upsampling are exact fp32 with the values of wg_mr_haar_split / merge / upsample, written straight into the engine's planes.
+ * No autograd counterpart: the training step stays composed from the blocks.
+ *
+ * wg_mr_config: the arguments of MRWaveGlow(...) and the WN keyword arguments it forwards.  levels - 1 levels of `flows` flows each on
+ * the Haar differences (c_l = n_group / 2^(l+1) channels, conditioned on the level's average stacked on the upsampled mel, or on the
+ * average alone with super_resolution), then prior_flows flows on the last average, conditioned on the upsampled mel.  reverse_mode:
+ * the couplings and the PRIOR 1x1 convs swap their two directions, the level 1x1 convs never do (upstream builds them as
+ * InvertibleConv1x1(c, c), whose second argument is memory_efficient): in such a model a pass applies W^-1 at the levels where it
+ * applies W in the prior, and the sign of T log|det W| in logdet is per flow.
+ *
+ * Table ("table" of wg_mr_pack_weights): device pointers in the order of the model's state_dict(), wg_mr_param_count entries:
+ *     prior_invconv1x1.{k}.weight [c, c, 1]                          (k = 0 .. prior_flows-1)
+ *     prior_WNs.{k}.F.*             one WN each, see below
+ *     invconv1x1_list.{l}.{k}.weight [c_l, c_l, 1]                   (l = 0 .. levels-2, k = 0 .. flows-1)
+ *     WNs_list.{l}.{k}.F.*
+ * A WN is V, start, (layers.{i}.W, layers.{i}.W_o) x depth as (weight_g, weight_v) pairs, then end.weight: 4 + 4 depth + 1 entries;
+ * with bias every conv's bias stands in front of its pair and end.bias behind end.weight (the state dict's order), + 2 + 2 depth + 1.
+ * A NULL weight_g means the conv carries a plain weight in its weight_v slot (weight norm removed); nothing else may be NULL.
+ *
+ * pack_weights (once per weight change, not per call): every WN as wg_wn_pack_weights packs it at the block's own (in_ch, aux_ch), and
+ * per 1x1 what wg_invconv_apply forms per call: W, W^-1, log|det W| (NaN for a negative determinant).
+ *
+ * forward / inverse: audio (z) [B, N] read as [B, T, n_group], h [B, n_mels, F] with T <= F (hop_size / n_group); the latent holds the
+ * levels' differences and the prior's average at the channel offsets of z_split_sizes.  logdet[B] = sum over flows of (+-) T log|det W|
+ * + the per-item sum of log_s, summed in a fixed order: two runs give the same bits.  The inputs are only read.  Everything is enqueued on
+ * `stream` in one linear chain: no allocation, no synchronisation, no read-back, so the call can be captured into a graph.
+ *
+ * check: WG_OK, or why the passes do not serve the call, before anything is launched (it needs no device): what MRWaveGlow's
+ * constructor refuses -- n_group no multiple of 2^levels, hop_size < n_group --, a precision outside WG_PREC_* and a depth outside
+ * 1 .. 16 (WG_EINVAL);
+ * n_group > 32, no flow at all (prior_flows = 0 with flows = 0 or levels = 1) or more than 64, and whatever the WN kernels refuse for one
+ * of the (in_ch, aux_ch) pairs: channels no multiple of 32, an even or > 9 radix (WG_EUNSUPPORTED); N % n_group or
+ * T > F (hop_size / n_group) (WG_ESHAPE); B > 65535 or B N past 2^31 - 1 (WG_EUNSUPPORTED).
+ * workspace_bytes / packed_bytes / param_count return 0 for a configuration (or shape) the check refuses. */
+typedef struct wg_mr_config {
+    int32_t prior_flows, flows, levels, n_group, hop_size, n_mels, super_resolution, reverse_mode;
+    int32_t dilation_channels, residual_channels, skip_channels, depth, radix, bias;
+    int32_t precision;
+} wg_mr_config;
+int    wg_mr_check(const wg_mr_config *cfg, int B, int N, int F);
+int    wg_mr_param_count(const wg_mr_config *cfg);
+size_t wg_mr_packed_bytes(const wg_mr_config *cfg);
+size_t wg_mr_workspace_bytes(const wg_mr_config *cfg, int B, int N);
+int    wg_mr_pack_weights(const wg_mr_config *cfg, const void *const *table, void *packed, void *stream);
+int    wg_mr_forward(const wg_mr_config *cfg, const void *packed, const float *audio, const float *h, int B, int N, int F,
+                     float *z, float *logdet, void *ws, size_t ws_bytes, void *stream);
+int    wg_mr_inverse(const wg_mr_config *cfg, const void *packed, const float *z, const float *h, int B, int N, int F,
+                     float *x, float *logdet, void *ws, size_t ws_bytes, void *stream);
+/* diagnostics, like the other wg_stat_*: passes run by this process */
+long long wg_stat_mr_pass_calls(void);
+/* The passes' plane kernels on their own, through the passes' launch helpers (what the tests measure them through).  A plane is
+ * [B][rows][P] floats, P = H + roundup(T, 128) + H, column t of a row at H + t (plane_geo gives H and P for T columns and a halo of at
+ * least `halo`); a kernel writes columns [0, T) of the rows it owns and nothing else.
+ * plane_split: the c channels of `audio` [B, T c] read as [B, T, c], or rows [0, c) of the plane `src` (exactly one of the two) ->
+ *   diff = x1 - x0 into rows [diff_ch0, + c/2) of `diff`, avg = (x0 + x1) / 2 into rows [0, c/2) of `cond` and (nullable) rows
+ *   [avg_ch0, + c/2) of `avg`.
+ * plane_merge: rows [0, c/2) of `avg` and rows [diff_ch0, + c/2) of `diff` -> avg -+ diff / 2 at rows (2i, 2i + 1) of the plane `out`, or
+ *   into `audio` [B, T c] as [B, T, c] (exactly one of the two).
+ * plane_upsample: wg_mr_upsample's values into rows [ch0[j], + n_mels) of each of the nd <= 7 planes, formed once. */
+int    wg_mr_plane_geo(int T, int halo, int *H, int *P);
+int    wg_mr_plane_split(const float *audio, const float *src, int src_rows, int B, int T, int halo, int c, float *diff, int diff_rows,
+                         int diff_ch0, float *cond, int cond_rows, float *avg, int avg_rows, int avg_ch0, void *stream);
+int    wg_mr_plane_merge(const float *avg, int avg_rows, const float *diff, int diff_rows, int diff_ch0, int B, int T, int halo, int c,
+                         float *out, int out_rows, float *audio, void *stream);
+int    wg_mr_plane_upsample(const float *h, int B, int n_mels, int F, int s, int T, int halo, int nd, float *const *planes, const int *rows,
+                            const int *ch0, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
